@@ -15,12 +15,18 @@ is one rank; without RANK, `--gpus N` spawns N fresh rank processes itself (befo
 anything touches a GPU in this process), the way `kopia benchmark splitter
 --parallel` runs N splitters at once (cli/command_benchmark.go:67-82).
 
-Prints ONE JSON line on rank 0 (the driver's contract).  Extra keys:
-  roofline     — the dominant kernel: rolled (algorithmic) bytes / kernel time vs
-                 HBM peak, plus the rocprofv3-measured physical HBM rate
+Prints ONE JSON line on rank 0 (the driver's contract).  A plain run sets up, warms
+up, times `--steps` launches and prints the line; its only extra key beside the
+headline figures is
+  roofline     — the dominant kernel: rolled (algorithmic) bytes / kernel time of the
+                 timed steps vs HBM peak, plus the rocprofv3-measured physical HBM rate
+`--dump-outputs DIR` also writes the cut lists the last timed step produced (dump_outputs).
+`--full` adds the legs that take runs of their own (rank 0, N=1 only):
   cpu_baseline — the oracle's C restatement of the reference Go loop on this host's
-                 cores, 1 thread and all usable threads (rank 0, N=1 only)
+                 cores, 1 thread and all usable threads; checks the GPU cuts, too
   host_inclusive_gib_s — host buffers -> H2D -> kernel -> D2H (kcdc_split_batch_host)
+  hash, pipeline, encrypt, encrypt_aes — the stages downstream of the cut, with their
+                 parity samples and CPU baselines
 """
 from __future__ import annotations
 
@@ -122,6 +128,33 @@ def aggregate(per_rank: list, steps: int) -> dict:
     return {"value": round(total / GiB / elapsed, 3), "elapsed_s": elapsed,
             "ms_per_step": round(elapsed / steps * 1e3, 4),
             "per_gpu_gib_s": [round(r["bytes_per_step"] * steps / GiB / r["own_s"], 3) for r in per_rank]}
+
+
+# ---------------------------------------------------------- --dump-outputs
+DUMP_LIMIT = 64 * 1000 * 1000  # bytes over all files of one dump
+
+
+def dump_outputs(dirpath: str, cut_lists: list, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: what the timed path's last step left for its caller, the cut list of
+    every stream (end offsets of its chunks within the stream), as float64 (exact: the offsets
+    are below 2^53):
+      streams.npy [k]  the indices of the dumped streams within this rank's shard, ascending
+      counts.npy  [k]  cuts of each dumped stream
+      cuts.npy    [sum(counts)]  their cut lists, one stream after another
+    All streams when that fits this rank's share of DUMP_LIMIT, else a fixed sample of them (a
+    permutation seeded with SEED, taken while it fits).  On N > 1 ranks the names carry `.rank<r>`."""
+    n = len(cut_lists)
+    sizes = np.array([c.size for c in cut_lists], dtype=np.int64)
+    budget = DUMP_LIMIT // world // 8 - 64  # float64 entries of this rank; 64 for the three .npy headers
+    order = np.random.default_rng(SEED).permutation(n)
+    need = np.cumsum(sizes[order] + 2)
+    sel = np.sort(order[: int(np.searchsorted(need, budget, side="right"))]) if n and need[-1] > budget \
+        else np.arange(n)
+    cuts = np.concatenate([cut_lists[i] for i in sel]).astype(np.float64) if sel.size else np.zeros(0, np.float64)
+    os.makedirs(dirpath, exist_ok=True)
+    tag = f".rank{rank}" if world > 1 else ""
+    for nm, a in (("streams", sel.astype(np.float64)), ("counts", sizes[sel].astype(np.float64)), ("cuts", cuts)):
+        np.save(os.path.join(dirpath, f"{nm}{tag}.npy"), a)
 
 
 # ------------------------------------------------------------- roofline
@@ -359,6 +392,8 @@ def bench_batch(args, comm: Comm):
     kern_ms = e0.elapsed_time(e1) / args.steps
 
     cuts = batch.read_cuts(b)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cuts, rank, world)
     rolled = sum(rolled_bytes(c, int(info.min_size)) for c in cuts)
     per = comm.gather({"bytes_per_step": ns * L, "elapsed_s": elapsed, "own_s": own, "kernel_ms": kern_ms,
                        "rolled": rolled})
@@ -386,15 +421,16 @@ def bench_batch(args, comm: Comm):
         out["roofline"]["hot_loop_frac"] = round(out["roofline"]["hot_loop_alone_ms"] / kern_ms, 3)
     out["cut_stats"] = {"chunks": int(sum(c.size for c in cuts)), "rolled_fraction": round(rolled / (ns * L), 4)}
 
-    if args.hash and rank == 0 and world == 1:
+    legs = args.full and rank == 0 and world == 1  # everything below takes runs of its own
+    if legs and args.hash:
         out["hash"] = bench_hash(args, data, ns, L, cuts, dev)
-    if args.encrypt and args.hash and rank == 0 and world == 1 and args.pipeline_slots > 0:
+    if legs and args.encrypt and args.hash and args.pipeline_slots > 0:
         out["pipeline"] = bench_pipeline(args, data, ns, L, cuts, dev)
-    if args.encrypt and rank == 0 and world == 1:
+    if legs and args.encrypt:
         out["encrypt"] = bench_encrypt(args, data, ns, L, cuts, dev)
         out["encrypt_aes"] = bench_encrypt(args, data, ns, L, cuts, dev, "AES256-GCM-HMAC-SHA256")
 
-    if rank == 0 and world == 1 and not args.no_host_inclusive:
+    if legs and not args.no_host_inclusive:
         # host-inclusive: pageable host buffers -> H2D -> kernel -> D2H (kcdc_split_batch_host)
         nh = min(ns, 1024)
         host = data[: nh * L].cpu().numpy()
@@ -409,7 +445,7 @@ def bench_batch(args, comm: Comm):
         out["host_inclusive_vs_pageable_h2d"] = round(out["host_inclusive_gib_s"] / out["h2d_gib_s"]["pageable"], 3)
         del host, views
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if legs and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(name, ns, L, cuts)
         if args.config == 2:
             out["cpu_baseline"]["config1_gb_s_1thread"] = cpu_config1()
@@ -718,7 +754,7 @@ def bench_long(args, comm: Comm):
     torch.cuda.synchronize(dev)
     warm_steps, warm_s = warm_up(lambda: batch.split_long_device(name, data.data_ptr(), L, dev, stream), 1,
                                  args.warmup_min_s, dev)
-    steps = max(1, min(args.steps, 10))
+    steps = max(1, args.steps)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
     comm.barrier()
     t0 = time.perf_counter()
@@ -732,6 +768,8 @@ def bench_long(args, comm: Comm):
     elapsed = time.perf_counter() - t0
     ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
     got = batch.read_long(cuts, count)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [batch.read_long(_c, _n)], comm.rank, comm.world)
     per = comm.gather({"bytes_per_step": L, "elapsed_s": elapsed, "own_s": own})
     agg = aggregate(per, steps)
     out = {"metric": METRIC, "value": agg["value"], "unit": "GiB/s", "n_gpus": comm.world, "steps": steps,
@@ -746,7 +784,7 @@ def bench_long(args, comm: Comm):
     out["roofline"] = roofline("kcdc::dev::cand_scan_rk_kernel" if rk else "kcdc::dev::cand_scan_dma_kernel<true>",
                                "config3" + ("-rk" if rk else ""), ms, L, L)
     out["roofline"]["algorithmic_bytes_def"] = "every stream byte (the full-scan candidate pass reads each once)"
-    if comm.rank == 0 and comm.world == 1 and not args.no_cpu_baseline:
+    if args.full and comm.rank == 0 and comm.world == 1 and not args.no_cpu_baseline:
         # the oracle's single sequential pass over the same bytes: the streaming splitter fed
         # 256 MiB slices generated ahead on other threads (only the split is timed)
         from oracle import coracle
@@ -810,7 +848,7 @@ def bench_files(args, comm: Comm):
         return time.perf_counter() - t0, own, res
 
     name = args.splitter
-    steps = max(1, min(args.steps, 10))
+    steps = max(1, args.steps)
     elapsed, own, res = run(name, steps, max(1, min(args.warmup, 2)))
     step_ms = ev["step_ms"]
     agg = aggregate(comm.gather({"bytes_per_step": total, "elapsed_s": elapsed, "own_s": own}), steps)
@@ -824,6 +862,8 @@ def bench_files(args, comm: Comm):
                       "parallelism": f"LPT file sharding x{world}, no data-path collectives"},
            "per_gpu_gib_s": agg["per_gpu_gib_s"]}
     got = batch.read_files(*res)
+    if args.dump_outputs:  # in this rank's order of files (ascending size)
+        dump_outputs(args.dump_outputs, got, rank, world)
     info = ks.lookup(name)
     if int(info.kind) != 0:  # FIXED names read no data: no roofline
         # The step's kernels (batch kernel for the small files, the long path's scan/prefix/resolve
@@ -835,7 +875,7 @@ def bench_files(args, comm: Comm):
         out["roofline"]["kernel_def"] = ("every kernel of one kcdc_split_files_device call, one HIP event pair around "
                                          "the K steps on the launch stream")
         out["cut_stats"] = {"chunks": int(sum(c.size for c in got)), "rolled_fraction": round(rolled / max(total, 1), 4)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # cpu_baseline leg: the oracle's C restatement on a sample of this rank's files
         # (the 64 smallest, every 8th and the 2 largest), which also checks their GPU cuts
         from oracle import coracle
@@ -923,6 +963,11 @@ def parse(argv):
     ap.add_argument("--warmup-min-s", type=float, default=0.3,
                     help="keep taking untimed warm-up steps until this many seconds have passed "
                          "(the clock ramps after idle); 0: exactly --warmup steps")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: also run the legs that take runs of their own (CPU baselines and oracle parity, "
+                         "host-inclusive rate, content hash, pipeline, encryption); --no-* drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the cut lists of the last timed step as DIR/{streams,counts,cuts}.npy (float64)")
     ap.add_argument("--splitter", default="DYNAMIC-4M-BUZHASH")
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--stream-mib", type=int, default=4)
@@ -934,15 +979,15 @@ def parse(argv):
     ap.add_argument("--long-gib", type=int, default=64, help="config 3 stream size")
     ap.add_argument("--files-gib", type=int, default=32, help="config 5 bytes per GPU (256 GiB over 8 GPUs)")
     ap.add_argument("--all-names", action="store_true", help="config 5: also time every registered name")
-    ap.add_argument("--hash", default="BLAKE2B-256-128", help="configs 2/4, one GPU: also hash every chunk on "
+    ap.add_argument("--hash", default="BLAKE2B-256-128", help="--full, configs 2/4, one GPU: also hash every chunk on "
                     "the device with this content hash (§8f #2; default Kopia's BLAKE2B-256-128)")
     ap.add_argument("--no-hash", action="store_true", help="skip the content-hash leg")
     ap.add_argument("--pipeline-slots", type=int, default=3, help="split->hash->seal batches in flight (0: skip)")
     ap.add_argument("--pipeline-batches", type=int, default=12, help="batches through the overlapped pipeline")
     ap.add_argument("--pipeline-hash", default="BLAKE3-256-128", help="second hash timed through the pipeline")
     ap.add_argument("--encrypt", action="store_true", default=True,
-                    help="configs 2/4, one GPU: also seal/open every chunk with CHACHA20-POLY1305-HMAC-SHA256 "
-                         "(§8f #4; on by default)")
+                    help="--full, configs 2/4, one GPU: also seal/open every chunk with "
+                         "CHACHA20-POLY1305-HMAC-SHA256 (§8f #4; on by default)")
     ap.add_argument("--no-encrypt", action="store_true", help="skip the encryption leg")
     ap.add_argument("--hash-inflight", type=int, default=24, help="--hash: chunk tables per launch, throughput figure")
     args = ap.parse_args(argv)

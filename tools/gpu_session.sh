@@ -7,8 +7,8 @@
 # steps:
 #   suite            pytest -m gpu (thread timeouts), then smoke()
 #   tests:PATTERN    pytest -m gpu -k PATTERN (e.g. tests:writer)
-#   bench            the driver's default line: bench.py --gpus 1 --steps 20 --warmup 5
-#   bench:ARGS       bench.py with ARGS (commas for spaces: bench:--config,4)
+#   bench            the driver's default line with every leg: bench.py --full --gpus 1 --steps 20 --warmup 5
+#   bench:ARGS       bench.py with ARGS (commas for spaces: bench:--config,4; add --full for the legs)
 #   prof             the default bench line under rocprofv3 --kernel-trace --stats, then its
 #                    FETCH_SIZE pass (separate runs: no PMC with tracing)
 #   prof:TAG:ARGS    the same for bench.py ARGS (commas for spaces), files named TAG_*
@@ -43,7 +43,7 @@ for step in "$@"; do
       timeout -k 10 600 python -u -m pytest tests -m gpu -x -v -k "$k" --timeout 200 --timeout-method thread > "$OUT/tests_$k.log" 2>&1
       rc=$?; tail -3 "$OUT/tests_$k.log"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit $?
+      timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit $?
       tail -c 600 "$OUT/bench_default.json" ;;
     bench:*)
       a=$(args "${step#bench:}"); t=$(echo "$a" | tr -c 'A-Za-z0-9' '_')
