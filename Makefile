@@ -51,7 +51,8 @@ build/group_bench: tools/group_bench.cpp include/kcdc.h $(LIB)
 .PHONY: all oracle clean asm
 
 # ---- experiment builds (A/B of compile-time tunables through tools/kbench.py; not the product)
-# e.g. make variants VARIANTS="gap1:-DKCDC_HELP_GAP=1u lane1k:-DKCDC_LANE_MAX=1024"
+# e.g. make variants VARIANTS="base: diag:-DKCDC_HELP_DIAG=1"  (name:flags, flags comma-separated;
+# the batch kernels' tunables are constants now: a variant of one is a patched source tree built here)
 VARIANTS ?=
 variants:
 	@mkdir -p build/variants

@@ -411,6 +411,8 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
  *   KCDC_TEST_LANE_CAP    buzhash batch launches: bytes per lane segment (a tile is 64 of them),
  *                         a power of two in [256, 4096]; 0: the default (avg / 256 within
  *                         [256, 2048]).  Other tile geometries for the same cuts.
+ *   KCDC_TEST_HELP_WINDOW both batch kernels: tiles of a region published to helpers at a time,
+ *                         in [3, 254]; 255: whole regions; 0: the default (the launch's rule)
  * kcdc_test_occupy: occupy `nwg` CUs (one workgroup with all of the CU's LDS each) for
  * `usec` microseconds on `hip_stream`, e.g. to run a batch beside a kernel that holds CUs.
  * kcdc_test_queue_stat: after the last pipelined batch launch has finished (synchronise
@@ -430,6 +432,7 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
 #define KCDC_TEST_NO_HELP 6
 #define KCDC_TEST_ID_RING 7
 #define KCDC_TEST_LANE_CAP 8
+#define KCDC_TEST_HELP_WINDOW 9
 int kcdc_test_set(int32_t key, int64_t value);
 int kcdc_test_occupy(uint32_t nwg, uint32_t usec, void* hip_stream);
 #define KCDC_TEST_STAT_GIVEUPS 1

@@ -49,14 +49,8 @@ constexpr int kWave = 64;
 constexpr int kBlk = 128;               // bytes per lane per step (one cache line)
 constexpr int kNdw = kBlk / 4;          // dwords per lane per step
 constexpr int64_t kLaneMax = 2048;      // max bytes per lane segment (tile = 64 x kLaneMax)
-#ifndef KCDC_TILE_DIV
-#define KCDC_TILE_DIV 256
-#endif
-constexpr uint64_t kTileDiv = KCDC_TILE_DIV;  // batch lane segments <= avg / kTileDiv (tiles ~ avg / 4), >= 256 B
-#ifndef KCDC_BUZ_LANE_MAX
-#define KCDC_BUZ_LANE_MAX 2048
-#endif
-constexpr uint64_t kBuzLaneMax = KCDC_BUZ_LANE_MAX;  // the buzhash batch kernel's lane segment cap
+constexpr uint64_t kTileDiv = 256;  // batch lane segments <= avg / kTileDiv (tiles ~ avg / 4), >= 256 B
+constexpr uint64_t kBuzLaneMax = 2048;  // the buzhash batch kernel's lane segment cap
 constexpr int kSchedWindow = 16;        // bytes per scheduling window in the warm-up / exact loops
 constexpr int kLookahead = 16;          // 128-byte steps: table reads issued this many bytes ahead (VGPR bound)
 
@@ -1047,31 +1041,16 @@ __device__ bool try_steal(const BatchArgs& a, int lane, uint32_t wg_waves) {
 //   row[k] {epoch:24 | state:8 | rel:32}: state 1 no candidate in tile k, 2 first candidate at
 //          ct0 + rel; anything else (or another epoch) pending.  Posted by atomic max, so a
 //          stale helper's older epoch never overwrites a newer result.
-#ifndef KCDC_HELP_EVERY
-#define KCDC_HELP_EVERY 2
-#endif
-#ifndef KCDC_HELP_GAP  // a region is open to helpers while top >= bottom + GAP (1 vs 2: 1.295 vs
-#define KCDC_HELP_GAP 1u  // 1.332 ms on config 2, same-process A/B, profiles/r04/third/)
-#endif
-#ifndef KCDC_HELP_MIN_AVG  // launch_split_batch's help policy: averages from here up (1 MiB)
-#define KCDC_HELP_MIN_AVG (1ull << 20)
-#endif
+// a region is open to helpers while top >= bottom + kHelpGap (1 vs 2: 1.295 vs 1.332 ms on
+// config 2, same-process A/B, profiles/r04/third/)
+constexpr uint32_t kHelpGap = 1u;
+constexpr uint64_t kHelpMinAvg = 1ull << 20;  // the launch's help policy (batch_plan): averages from here up (1 MiB)
 // Every region is published (a tail-only policy -- publish only in visits that began with no
 // stream waiting -- lost 2-10 % at 1M-4M; DESIGN.md §2.1, profiles/r05/help_tail_only/).
-__device__ __forceinline__ bool help_phase(int64_t budget) {
-    (void)budget;
-    return true;
-}
 constexpr int64_t kHelpSplit = 2;     // sub-tiles per help task (lane segments lane_cap / 2, >= 256 B)
 constexpr int kHelpTiles = 128;          // regions of up to 128 tiles take help (every registered name)
-#ifndef KCDC_HELP_MIN_TILES
-#define KCDC_HELP_MIN_TILES 3u
-#endif
-constexpr uint32_t kHelpMinTiles = KCDC_HELP_MIN_TILES;  // the owner's tile, its next one, and at least one more
-#ifndef KCDC_HELP_WAIT_TICKS
-#define KCDC_HELP_WAIT_TICKS 20000
-#endif
-constexpr uint64_t kHelpWaitTicks = KCDC_HELP_WAIT_TICKS;  // 200 us of s_memrealtime (a tile takes 15-40 us)
+constexpr uint32_t kHelpMinTiles = 3u;  // the owner's tile, its next one, and at least one more
+constexpr uint64_t kHelpWaitTicks = 20000;  // 200 us of s_memrealtime (a tile takes 15-40 us)
 __device__ __forceinline__ size_t help_params_off(uint32_t nw) { return 128ull * nw; }
 __device__ __forceinline__ size_t help_rows_off(uint32_t nw) { return 128ull * nw + 64ull * nw; }
 __device__ __forceinline__ size_t help_bits_off(uint32_t nw) { return help_rows_off(nw) + 8ull * kHelpTiles * nw; }
@@ -1244,9 +1223,9 @@ __device__ bool help_find(const BatchArgs& a, int lane, uint32_t me, uint32_t at
     const uint64_t c = g < nw ? ld_agent64(help_claim(a, g)) : 0ull;
     const uint32_t ep = static_cast<uint32_t>(c >> 40), top = static_cast<uint32_t>(c >> 20) & 0xFFFFFu,
                    bot = static_cast<uint32_t>(c) & 0xFFFFFu;
-    // claim only tiles >= bottom + KCDC_HELP_GAP - 1 (GAP 1: up to the owner's next tile, which the
+    // claim only tiles >= bottom + kHelpGap - 1 (gap 1: up to the owner's next tile, which the
     // owner then takes from the row instead of scanning it)
-    const bool open = ep != 0u && !(ep & kHelpClosed) && top >= bot + KCDC_HELP_GAP;
+    const bool open = ep != 0u && !(ep & kHelpClosed) && top >= bot + kHelpGap;
     const uint32_t key = open ? ((top - bot) << 6) | ((static_cast<uint32_t>(lane) + rot) & 63u) : 0u;
     uint32_t best = key;
 #pragma unroll
@@ -1292,7 +1271,7 @@ __device__ bool help_find(const BatchArgs& a, int lane, uint32_t me, uint32_t at
 //   in a row saw no stream finish they sleep s_sleep 32 (1.339-1.344 vs 1.363 ms on config 2,
 //   profiles/r03/buz/kbench_poll_*.log) and read the done counter every 4th poll.
 //   Help: a waiting wave looks for a tile to help with every kHelpEvery polls (help_find).
-constexpr uint32_t kPollAfter = 8, kDoneEvery = 4, kHelpEvery = KCDC_HELP_EVERY;
+constexpr uint32_t kPollAfter = 8, kDoneEvery = 4, kHelpEvery = 2;
 __device__ int presolve(const BatchArgs& a, int lane, uint32_t t, PStream& st, uint32_t wg_waves, uint32_t me,
                         bool can_help) {
     const uint32_t n = a.nstreams;
@@ -1418,13 +1397,337 @@ __device__ __forceinline__ int64_t pipe_quantum(int64_t backlog, int64_t q = kPi
 // keep 6 x 128 KiB = 768 KiB (512 KiB there: 1.334 vs 1.286 ms); 128K and 256K get 512 KiB.  Against
 // the constant 768 KiB in one process (profiles/r04/third/ab_quantum_tiles_*.log): 128K 3.415 vs
 // 3.639 ms, 256K 2.697 vs 2.843, 4M 1.296 vs 1.309; all bit-exact.
-#ifndef KCDC_QUANTUM_TILES
-#define KCDC_QUANTUM_TILES 6
-#endif
 __device__ __forceinline__ int64_t pipe_quantum_tiles(int64_t backlog, uint32_t lane_cap) {
-    constexpr int64_t kTiles = KCDC_QUANTUM_TILES, kMax = kTiles * kWave * 2048;  // (2 KiB lanes: 768 KiB)
+    constexpr int64_t kTiles = 6, kMax = kTiles * kWave * 2048;  // (2 KiB lanes: 768 KiB)
     const int64_t q = kTiles * kWave * static_cast<int64_t>(lane_cap);
     return pipe_quantum(backlog, q < (512 << 10) ? (512 << 10) : q > kMax ? kMax : q);
+}
+
+// ------------------------------------------------------------ the visit protocol
+// What split_batch_pipe_kernel and split_batch_rk_kernel share: taking streams from the ticketed
+// ring, publishing regions to helpers, the plan of a tile (claim, yield, next ticket), and what
+// follows a tile's scan (help post, cut, requeue, the next stream).  The kernels keep the feed,
+// the hash, the candidate checks and the steps at which the atomics and DMAs are issued.  All of
+// it is wave-uniform and inlined at one site per kernel (presolve and try_steal are large).
+constexpr uint32_t kHsPub = 1u << 16;     // the current region is published (claims are on)
+constexpr uint32_t kHsNeedPub = 1u << 17; // the region at cur.ct is new to this wave
+constexpr uint32_t kHsHelped = 1u << 18;  // the last claim saw helpers on the region: no yield
+struct Visit {
+    PStream cur;
+    int64_t budget = kNoYield;
+    // Help state of this wave's own slot (wave-uniform, packed: SGPRs are what these kernels run
+    // short of): hep = the epoch of the last publish; hs = the published region's tile count
+    // (bits 0-7), the index of the tile being scanned (8-15) and the kHs* flags.
+    uint32_t hep = 0, hs = kHsNeedPub;
+    // Pending blocking take (set right before jumping to the loop top, so none of it is live
+    // across the hash loop).
+    bool need_take = true;
+    uint32_t take_t = 0xFFFFFFFFu, take_claim = 0xFFFFFFFFu;
+    int64_t take_backlog = 0;
+    bool issued = false;  // this tile's first fill (buzhash: warm piece + step 0) is in flight
+    __device__ __forceinline__ uint32_t hK() const { return hs & 0xFFu; }
+    __device__ __forceinline__ uint32_t htile() const { return (hs >> 8) & 0xFFu; }
+    // Take at the loop top: ticket t (held), or ~0u for a fresh one.
+    __device__ __forceinline__ void take(uint32_t t, int64_t backlog) {
+        need_take = true;
+        take_t = t;
+        take_backlog = backlog;
+        take_claim = 0xFFFFFFFFu;
+    }
+};
+// The wave-uniform facts of the tile being scanned: visit_tile's plan, the kernel's claim and
+// prefetch results, and the atomics' raw values.
+struct Tile {
+    bool is_help, last_of_region;
+    int64_t ct, ct_next, hi;  // the tile [ct, ct_next) of the region ending at hi
+    bool switching, reserve, claim_next;
+    uint64_t ht_raw = 0;      // the next stream's ticket add, as returned to lane 0
+    uint32_t tk = 0;          // that ticket (set_ticket)
+    int64_t nbacklog = 0;
+    uint64_t pe_raw = 0;      // this stream's reserved entry, as returned to lane 0
+    bool res_issued = false;
+    bool claim_ok = false, claim_known;
+    bool next_issued = false;  // the region's next tile is prefetched
+    __device__ __forceinline__ void set_ticket(uint32_t ht_lo, uint32_t ht_hi) {
+        if (!switching) return;
+        const uint64_t ht = qht_value(ht_lo, ht_hi);
+        tk = static_cast<uint32_t>(ht);
+        nbacklog = static_cast<int64_t>(ht >> 32) + (reserve ? 1 : 0) - static_cast<int64_t>(tk) - 1;
+    }
+    // cw: the owner's claim word after this tile's add
+    __device__ __forceinline__ void claim_decode(Visit& v, uint64_t cw) {
+        const uint32_t top = static_cast<uint32_t>(cw >> 20) & 0xFFFFFu, bot = static_cast<uint32_t>(cw) & 0xFFFFFu;
+        claim_ok = static_cast<uint32_t>(cw >> 40) == v.hep && bot <= top;
+        if (top < v.hK()) v.hs |= kHsHelped;
+        claim_known = true;
+    }
+    // This stream's ring entry, reserved late (in the tile's last step or fill, else at its end).
+    __device__ __forceinline__ void reserve_entry(const BatchArgs& a, int lane) {
+        pe_raw = qht_add(a, lane, 1ull << 32);
+        res_issued = true;
+    }
+};
+
+// First ticket: preassigned (see init_ring_kernel), unless a waiting wave has requeued
+// this workgroup's streams before it started (try_steal): then take one from the counter.
+template <uint32_t WG_WAVES>
+__device__ __forceinline__ void visit_first_ticket(const BatchArgs& a, int lane, uint32_t wave, Visit& v) {
+    uint32_t claim = 1u;
+    if (lane == 0) {
+        claim = 0u;
+        __hip_atomic_compare_exchange_strong((gu32*)(a.queue + kQFlags + blockIdx.x), &claim, 1u,
+                                             __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const uint32_t t0 = first_ticket(blockIdx.x, wave);
+    const int64_t nw = static_cast<int64_t>(gridDim.x) * WG_WAVES;
+    v.take_t = t0 < a.nstreams ? t0 : 0xFFFFFFFFu;
+    v.take_backlog = static_cast<int64_t>(a.nstreams) - nw;
+    v.take_claim = t0 < a.nstreams ? (claim & 3u) : 0xFFFFFFFFu;
+}
+
+// The pending blocking take (v.take_t: a ticket already held, or ~0u to take one): the next
+// stream with a region to scan, or a help task; false when every stream is done.  No LDS-DMA
+// may be in flight.
+// v.take_claim: the first take's claim of this workgroup's preassigned tickets (lane 0's CAS
+// result: 0 or 1 ours, 2 the streams were requeued by try_steal), issued before the first
+// resolve and checked after it so its round trip overlaps the entry load; ~0u elsewhere
+// (a constant at those sites: no claim state stays live across the main loop).
+// quantum(backlog): the visit's byte budget.
+template <uint32_t WG_WAVES, class Quantum>
+__device__ __forceinline__ bool visit_take(const BatchArgs& a, int lane, uint32_t me, Visit& v, Quantum quantum) {
+    PStream& cur = v.cur;
+    uint32_t t = v.take_t, claim = v.take_claim;
+    v.need_take = false;
+    v.issued = false;
+    v.hs |= kHsNeedPub;
+    for (;;) {
+        int64_t backlog = v.take_backlog;  // queue depth behind a ticket already held (caller's estimate)
+        if (t == 0xFFFFFFFFu) {
+            const uint64_t ht = qht_take(a, lane, 1);
+            t = static_cast<uint32_t>(ht);
+            backlog = static_cast<int64_t>(ht >> 32) - static_cast<int64_t>(t) - 1;
+        }
+        const uint32_t held = t;
+        const int r = presolve(a, lane, held, cur, WG_WAVES, me, a.help != nullptr && claim == 0xFFFFFFFFu);
+        if (r == 0) return false;
+        if (r == 3) {  // a help task; the ticket stays held (in cap, unused by help tasks, and in memory)
+            held_put(a, lane, me, held);
+            cur.cap = held;
+            uniformize(cur);
+            return true;
+        }
+        t = 0xFFFFFFFFu;
+        if (claim != 0xFFFFFFFFu) {
+            const bool requeued = bcast(claim) == 2u;
+            claim = 0xFFFFFFFFu;
+            if (requeued) continue;  // requeued by another wave: take a fresh ticket
+        }
+        if (r == 2) continue;  // tombstone
+        uniformize(cur);
+        if (!pcheck(a, lane, cur, held, 1)) return false;
+        v.budget = quantum(backlog);
+        if (pstream_region(a, cur, lane)) return true;
+        if (lane == 0) {  // nothing left to scan
+            a.counts[cur.sid] = cur.cnt;
+            add_agent(a.queue + kQDone, 1u);
+        }
+    }
+}
+
+// Loop top, diagnostic builds: wave-uniform control values held lane-divergent, before the
+// blocking take and before the tile.
+__device__ __forceinline__ void visit_diag_take(const BatchArgs& a, int lane, const Visit& v) {
+#if KCDC_HELP_DIAG
+    diag_record(a, lane, divergent_bit(v.need_take, 0) | divergent_bit(v.take_t, 1) | divergent_bit(v.issued, 2));
+#endif
+}
+__device__ __forceinline__ void visit_diag_tile(const BatchArgs& a, int lane, const Visit& v) {
+#if KCDC_HELP_DIAG
+    diag_record(a, lane, divergent_bit(v.hs, 3) | divergent_bit(v.hep, 4) | divergent_bit(v.cur.sid, 5) |
+                             divergent_bit(static_cast<uint32_t>(v.cur.cap), 6) |
+                             divergent_bit(static_cast<uint32_t>(v.cur.ct), 7) |
+                             divergent_bit(static_cast<uint32_t>(v.budget), 8));
+#endif
+}
+
+// The plan of the tile [v.cur.ct, + tile_bytes) of the region ending at hi (T: bytes per full
+// own tile): publishes a region new to this wave, and issues the next stream's ticket add when
+// this is the visit's last tile.
+__device__ __forceinline__ Tile visit_tile(const BatchArgs& a, int lane, uint32_t me, Visit& v, bool is_help, int64_t hi,
+                                           int64_t tile_bytes, int64_t T) {
+    const PStream& cur = v.cur;
+    Tile t;
+    t.is_help = is_help;
+    t.ct = cur.ct;
+    t.ct_next = t.ct + tile_bytes;
+    t.hi = hi;
+    t.last_of_region = t.ct_next > hi;
+    // A region new to this wave: publish it when it is long enough to share.
+    if ((v.hs & kHsNeedPub) && !is_help) {
+        const uint32_t K = static_cast<uint32_t>((hi - t.ct + T) / T);
+        v.hs = 0;
+        if (a.help && K >= kHelpMinTiles && K <= static_cast<uint32_t>(kHelpTiles)) {
+            // a window of the region (help_window tiles from here), re-published as the owner
+            // passes its end
+            const uint32_t Kw = a.help_window && K > a.help_window ? a.help_window : K;
+            v.hep++;
+            v.hs = kHsPub | Kw;
+            help_publish(a, lane, me, v.hep, cur, t.ct, Kw < K ? t.ct + static_cast<int64_t>(Kw) * T - 1 : hi, Kw, T);
+        }
+    }
+    // The owner's claim on its next tile: an atomic add on its slot's bottom, issued and read
+    // back by the kernel inside the tile.
+    const bool claim_next_r = (v.hs & kHsPub) && !is_help && !t.last_of_region && v.htile() + 1u < v.hK();
+    // (a help task never yields: its wave's budget is the last own visit's leftover, and a
+    // reservation made here would never be written -- its ticket's taker would wait to the end)
+    const bool budget_out = !is_help && !(v.hs & kHsHelped) && v.budget - tile_bytes <= 0;  // (with helpers: no yield)
+    bool ends_nocand = false;  // no candidate in this tile => the stream is finished
+    if (!is_help && t.last_of_region) {
+        const int64_t mx = static_cast<int64_t>(a.max_size);
+        const int64_t s2 = cur.s + mx - 1 <= cur.n - 1 ? cur.s + mx : cur.n;
+        ends_nocand = s2 >= cur.n || s2 + static_cast<int64_t>(a.min_size) - 1 >= cur.n;
+    }
+    // The visit's last tile (absent a candidate): take the next ticket now, and reserve
+    // this stream's entry too when it will be yielded -- one atomic, hidden by the DMAs.
+    t.switching = !is_help && (budget_out || ends_nocand);
+    t.reserve = budget_out && !ends_nocand;
+    t.claim_next = claim_next_r && !t.switching;  // a yielding owner claims nothing more
+    t.claim_known = !t.claim_next;
+    if (t.switching) t.ht_raw = qht_add(a, lane, 1);  // the next stream's ticket
+    return t;
+}
+
+// After a tile's scan (f: the coordinate of its first candidate, or -1): a help task posts and
+// goes on or ends; an owner resolves the region's cut (a hit, the forced cut, the helpers'
+// posts, or the next tile), then goes on with its stream or requeues it.  T: bytes per full own
+// tile (a parameter again: kept in the Tile it would live across the hash loop).  True: back to
+// the loop top (same stream, or v.need_take); false: the wave switches streams (visit_adopt follows).
+__device__ __forceinline__ bool visit_resolve(const BatchArgs& a, int lane, uint32_t me, Visit& v, Tile& t, int64_t f,
+                                              int64_t T) {
+    PStream& cur = v.cur;
+    if (t.reserve && !t.res_issued) t.reserve_entry(a, lane);
+    if (t.is_help) {
+        bool done = true;
+        if (f >= 0 || t.last_of_region) {  // post the tile's first candidate to its owner's row
+            help_post(a, lane, static_cast<uint32_t>(cur.cb), cur.epoch, static_cast<uint32_t>(cur.cnt), cur.s, f);
+        } else {  // the next sub-tile (prefetched), unless the owner has closed the region
+            const uint64_t w = ld_agent64(help_claim(a, static_cast<uint32_t>(cur.cb)));
+            done = static_cast<uint32_t>(qht_value(static_cast<uint32_t>(w), static_cast<uint32_t>(w >> 32)) >> 40) !=
+                   cur.epoch;
+        }
+        if (!done) {
+            cur.ct = t.ct_next;
+            v.issued = t.next_issued;
+            return true;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the post, or a dropped prefetch
+        // (the held ticket is taken back from memory, here where both ending paths have joined:
+        // DESIGN.md §2.1c)
+        v.take(held_get(a, lane, me, static_cast<uint32_t>(cur.cap)), 0);
+        return true;
+    }
+    bool region_changed = true;
+    const int64_t mx = static_cast<int64_t>(a.max_size);
+    const int64_t forced = cur.s + mx - 1 <= cur.n - 1 ? cur.s + mx : cur.n;  // max-size cut / the end
+    int64_t cut = -1;  // this region's cut, once known
+    if (f >= 0) {
+        cut = f - cur.off0 + 1;
+    } else if (t.last_of_region) {  // forced cut at max size (splitter_buzhash32.go:60-64,
+        cut = forced;               // splitter_rabinkarp64.go:60-64) or the end
+    } else if (t.claim_next && !t.claim_ok) {  // the helpers hold the rest of the region
+        const int64_t ct0 = t.ct - static_cast<int64_t>(v.htile()) * T;  // the published tile 0
+        const int64_t r = help_wait(a, lane, me, v.hep, v.htile() + 1u, v.hK(), ct0);
+        const int64_t wend = ct0 + static_cast<int64_t>(v.hK()) * T;  // past the published window
+        if (r >= 0) {
+            cut = r - cur.off0 + 1;
+        } else if (r == -1 && wend <= t.hi) {  // no candidate in the window: publish the next one
+            cur.ct = wend;
+            help_close(a, lane, me, v.hep);
+            v.hs = kHsNeedPub;
+            region_changed = false;
+        } else if (r == -1) {
+            cut = forced;
+        } else {  // a tile still pending: scan on from it, unshared
+            cur.ct = ct0 + (-2 - r) * T;
+            help_close(a, lane, me, v.hep);
+            v.hs = 0;
+            region_changed = false;
+        }
+    } else {
+        cur.ct = t.ct_next;
+        v.hs += 1u << 8;  // htile++
+        v.budget -= t.ct_next - t.ct;
+        region_changed = false;
+        if ((v.hs & kHsPub) && v.htile() >= v.hK()) {  // past its published window: the next one
+            help_close(a, lane, me, v.hep);
+            v.hs = kHsNeedPub;
+        }
+    }
+    if (cut >= 0) {
+        emit_cut(a, cur, lane, cut);
+        cur.s = cut;
+        cur.ct = -1;
+    }
+    if (region_changed) {
+        if (v.hs & kHsPub) help_close(a, lane, me, v.hep);
+        v.hs = kHsNeedPub;
+    }
+    const bool live = pstream_region(a, cur, lane);
+    if (!live && lane == 0) {
+        a.counts[cur.sid] = cur.cnt;
+        add_agent(a.queue + kQDone, 1u);
+    }
+    if (!t.switching && live) {  // same stream, next tile
+        v.issued = t.next_issued && !region_changed;
+        if (t.next_issued && region_changed) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stale prefetch
+        return true;
+    }
+    // ---- switch streams: requeue this one first (its reserve atomic was issued in the
+    // last step, so no prefetch DMA is in flight behind it)
+    if (v.hs & kHsPub) help_close(a, lane, me, v.hep);  // a yielded region is not ours to share any more
+    v.hs = kHsNeedPub;
+    if (t.reserve) {
+        const uint32_t pe = static_cast<uint32_t>(
+            qht_value(static_cast<uint32_t>(t.pe_raw), static_cast<uint32_t>(t.pe_raw >> 32)) >> 32);
+        pwrite(a, lane, pe, cur, !live);
+    } else if (live) {  // a candidate kept the stream alive past its predicted last tile
+        const uint64_t ht = qht_take(a, lane, 1ull << 32);
+        pwrite(a, lane, static_cast<uint32_t>(ht >> 32), cur, false);
+    }
+    return false;
+}
+
+// The wave switches streams (visit_resolve returned false): adopt the next stream from its ring
+// entry, which the kernel's DMA of ticket tk has landed at `entry` (entry_landed; the DMA is
+// drained), or leave the ticket to a blocking take at the loop top.  tk is ~0u when the tile took
+// no ticket (the stream ended on a candidate: a fresh one is taken); nbacklog: the queue depth
+// behind tk.  prefetch(nx): the kernel may issue the adopted
+// stream's first tile and return true.  False when the wave must exit (a failed check).
+template <class Quantum, class Prefetch>
+__device__ __forceinline__ bool visit_adopt(const BatchArgs& a, int lane, Visit& v, const uint8_t* entry, bool entry_landed,
+                                            uint32_t tk, int64_t nbacklog, Quantum quantum, Prefetch prefetch) {
+    if (entry_landed) {
+        const u32x4 ev = *reinterpret_cast<const u32x4*>(entry + 16 * (lane & 7));
+        if (pentry_ok(ev, lane, tk) && static_cast<uint32_t>(__builtin_amdgcn_readlane(ev.w, 0)) != kTombstone) {
+            PStream nx;
+            pentry_decode(nx, ev);
+            uniformize(nx);
+            if (!pcheck(a, lane, nx, tk, 2)) return false;
+            v.issued = prefetch(nx);
+            v.cur = nx;
+            v.budget = quantum(nbacklog);
+            if (pstream_region(a, v.cur, lane)) return true;
+            if (lane == 0) {  // nothing left to scan in it
+                a.counts[v.cur.sid] = v.cur.cnt;
+                add_agent(a.queue + kQDone, 1u);
+            }
+            v.take(0xFFFFFFFFu, 0);
+            return true;
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no prefetch may remain in flight
+    v.take(tk, nbacklog);
+    return true;
 }
 
 template <bool TOP>
@@ -1448,7 +1751,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
 #if KCDC_TRACE  // per wave at trace[8 * global wave]: start, end, ticks in blocking takes, the last take's
                 // start, help tiles, their ticks, the end of the wave's last own tile, own tiles
     const uint32_t gw = blockIdx.x * kDmaWaves + wave;
-    uint64_t tr_block = 0, tr_nblock = 0, tr_last = 0, tr_help = 0, tr_help_t = 0, tr_own_end = 0, tr_own = 0;
+    uint64_t tr_block = 0, tr_last = 0, tr_help = 0, tr_help_t = 0, tr_own_end = 0, tr_own = 0;
     if (lane == 0) a.trace[8 * gw] = __builtin_amdgcn_s_memrealtime();
 #define KCDC_PRET                                                                 \
     do {                                                                          \
@@ -1467,115 +1770,33 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
 #define KCDC_PRET return
 #endif
     const uint32_t lim = TOP ? a.buz_lim : 0u;
-    const int64_t mx = static_cast<int64_t>(a.max_size);
     // help sub-tiles halve the lane segments (>= 256 B): shift = sid's help bit & this (integer
     // arithmetic: a select on a bool here became a VALU-materialised shift next to the DMAs)
     const uint32_t help_shift = __builtin_amdgcn_readfirstlane(a.lane_cap >= 512u ? 1u : 0u);
     static_assert(kHelpSplit == 2, "help sub-tiles: one halving");
 
-    PStream cur;
-    int64_t budget = kNoYield;
-    // Help state of this wave's own slot (wave-uniform, packed: SGPRs are what this kernel runs
-    // short of): hep = the epoch of the last publish; hs = the published region's tile count
-    // (bits 0-7), the index of the tile being scanned (8-15) and the flags below.
-    uint32_t hep = 0, hs = 0;
-    constexpr uint32_t kHsPub = 1u << 16;     // the current region is published (claims are on)
-    constexpr uint32_t kHsNeedPub = 1u << 17; // the region at cur.ct is new to this wave
-    constexpr uint32_t kHsHelped = 1u << 18;  // the last claim saw helpers on the region: no yield
-    hs = kHsNeedPub;
-    auto hK = [&] { return hs & 0xFFu; };
-    auto htile = [&] { return (hs >> 8) & 0xFFu; };
-    // Blocking take of the next stream with a region to scan (t: a ticket already held,
-    // or ~0u to take one); false when every stream is done.  No LDS-DMA may be in flight.
-    // claim: the first take's claim of this workgroup's preassigned tickets (lane 0's CAS
-    // result: 0 or 1 ours, 2 the streams were requeued by try_steal), issued before the first
-    // resolve and checked after it so its round trip overlaps the entry load; ~0u elsewhere
-    // (a constant at those call sites: no claim state stays live across the main loop).
-    auto take_blocking = [&](uint32_t t, int64_t backlog_hint, uint32_t claim) -> bool {
-#if KCDC_TRACE
-        const uint64_t tb0 = __builtin_amdgcn_s_memrealtime();
-        tr_last = tb0;
-        struct Acc {
-            uint64_t t0, &sum, &cnt;
-            __device__ ~Acc() {
-                sum += __builtin_amdgcn_s_memrealtime() - t0;
-                cnt++;
-            }
-        } acc{tb0, tr_block, tr_nblock};
-#endif
-        for (;;) {
-            int64_t backlog = backlog_hint;  // queue depth behind a ticket already held (caller's estimate)
-            if (t == 0xFFFFFFFFu) {
-                const uint64_t ht = qht_take(a, lane, 1);
-                t = static_cast<uint32_t>(ht);
-                backlog = static_cast<int64_t>(ht >> 32) - static_cast<int64_t>(t) - 1;
-            }
-            const uint32_t held = t;
-            const int r = presolve(a, lane, held, cur, kDmaWaves, me, a.help != nullptr && claim == 0xFFFFFFFFu);
-            if (r == 0) return false;
-            if (r == 3) {  // a help task; the ticket stays held (in cap, unused by help tasks, and in memory)
-                held_put(a, lane, me, held);
-                cur.cap = held;
-                uniformize(cur);
-                return true;
-            }
-            t = 0xFFFFFFFFu;
-            if (claim != 0xFFFFFFFFu) {
-                const bool requeued = bcast(claim) == 2u;
-                claim = 0xFFFFFFFFu;
-                if (requeued) continue;  // requeued by another wave: take a fresh ticket
-            }
-            if (r == 2) continue;  // tombstone
-            uniformize(cur);
-            if (!pcheck(a, lane, cur, held, 1)) return false;
-            budget = pipe_quantum_tiles(backlog, a.lane_cap);
-            if (pstream_region(a, cur, lane)) return true;
-            if (lane == 0) {  // nothing left to scan
-                a.counts[cur.sid] = cur.cnt;
-                add_agent(a.queue + kQDone, 1u);
-            }
-        }
-    };
-    // Pending blocking take (set right before jumping to the loop top, so none of it is live
-    // across the hash loop).
-    bool need_take = true;
-    uint32_t take_t = 0xFFFFFFFFu, take_claim = 0xFFFFFFFFu;
-    int64_t take_backlog = 0;
-    {
-        // First ticket: preassigned (see init_ring_kernel), unless a waiting wave has requeued
-        // this workgroup's streams before it started (try_steal): then take one from the counter.
-        uint32_t claim = 1u;
-        if (lane == 0) {
-            claim = 0u;
-            __hip_atomic_compare_exchange_strong((gu32*)(a.queue + kQFlags + blockIdx.x), &claim, 1u,
-                                                 __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        const uint32_t t0 = first_ticket(blockIdx.x, wave);
-        const int64_t nw = static_cast<int64_t>(gridDim.x) * kDmaWaves;
-        take_t = t0 < a.nstreams ? t0 : 0xFFFFFFFFu;
-        take_backlog = static_cast<int64_t>(a.nstreams) - nw;
-        take_claim = t0 < a.nstreams ? (claim & 3u) : 0xFFFFFFFFu;
-    }
-    bool issued = false;  // this tile's warm piece + step 0 are in flight
+    Visit v;
+    PStream& cur = v.cur;
+    // The buzhash visit quantum (pipe_quantum_tiles) for visit_take and visit_adopt.
+    const auto quantum = [&](int64_t backlog) { return pipe_quantum_tiles(backlog, a.lane_cap); };
+    visit_first_ticket<kDmaWaves>(a, lane, wave, v);
     for (;;) {
-#if KCDC_HELP_DIAG
-        diag_record(a, lane, divergent_bit(need_take, 0) | divergent_bit(take_t, 1) | divergent_bit(issued, 2));
-#endif
+        visit_diag_take(a, lane, v);
         // The one blocking take site (inlined once: presolve and try_steal are large).
-        if (need_take) {
-            if (!take_blocking(take_t, take_backlog, take_claim)) KCDC_PRET;
-            need_take = false;
-            issued = false;
-            hs |= kHsNeedPub;
-        }
-#if KCDC_HELP_DIAG
-        diag_record(a, lane, divergent_bit(hs, 3) | divergent_bit(hep, 4) | divergent_bit(cur.sid, 5) |
-                                 divergent_bit(static_cast<uint32_t>(cur.cap), 6) |
-                                 divergent_bit(static_cast<uint32_t>(cur.ct), 7) |
-                                 divergent_bit(static_cast<uint32_t>(budget), 8));
+        if (v.need_take) {
+#if KCDC_TRACE
+            const uint64_t tb0 = __builtin_amdgcn_s_memrealtime();
+            tr_last = tb0;
 #endif
+            const bool taken = visit_take<kDmaWaves>(a, lane, me, v, quantum);
+#if KCDC_TRACE
+            tr_block += __builtin_amdgcn_s_memrealtime() - tb0;
+#endif
+            if (!taken) KCDC_PRET;
+        }
+        visit_diag_tile(a, lane, v);
         uniformize(cur);
-        if (!pcheck(a, lane, cur, 0xFFFFFFFFu, 5)) return;
+        if (!pcheck(a, lane, cur, 0xFFFFFFFFu, 5)) KCDC_PRET;
         const bool is_help = (cur.sid & kHelpBit) != 0;
 #if KCDC_TRACE
         const uint64_t tr_t0 = __builtin_amdgcn_s_memrealtime();
@@ -1588,46 +1809,17 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
         // the first one with a candidate, or when its owner has closed the region meanwhile.
         const int64_t lcap = static_cast<int64_t>(a.lane_cap >> ((cur.sid >> 31) & help_shift));
         const TileGeom g = tile_geom(cur.ct, hi, cur.abase, cur.off0, cur.off0 + cur.n, lcap);
-        const int64_t ct = cur.ct, ct_next = ct + kWave * g.L;
-        const bool last_of_region = ct_next > hi;
-        if (!issued) ptile_issue(cur, hi, wl32, sl32, lane, lcap);
-        // A region new to this wave: publish it when it is long enough to share.
-        if ((hs & kHsNeedPub) && !is_help) {
-            const int64_t T = kWave * static_cast<int64_t>(a.lane_cap);  // bytes per full tile
-            const uint32_t K = static_cast<uint32_t>((hi - ct + T) / T);
-            hs = 0;
-            if (a.help && help_phase(budget) && K >= kHelpMinTiles && K <= static_cast<uint32_t>(kHelpTiles)) {
-                // a window of the region (help_window tiles from here), re-published as the owner
-                // passes its end
-                const uint32_t Kw = a.help_window && K > a.help_window ? a.help_window : K;
-                hep++;
-                hs = kHsPub | Kw;
-                help_publish(a, lane, me, hep, cur, ct, Kw < K ? ct + static_cast<int64_t>(Kw) * T - 1 : hi, Kw, T);
-            }
-        }
-        // The owner's claim on its next tile (atomic add on its slot's bottom), issued in step 0
+        if (!v.issued) ptile_issue(cur, hi, wl32, sl32, lane, lcap);
+        // The owner's claim on its next tile (atomic add on its slot's bottom) is issued in step 0
         // behind the refill DMA and read in step 2 (or at the tile end for one- and two-step tiles).
-        const bool claim_next_r = (hs & kHsPub) && !is_help && !last_of_region && htile() + 1u < hK();
-        // (a help task never yields: its wave's budget is the last own visit's leftover, and a
-        // reservation made here would never be written -- its ticket's taker would wait to the end)
-        const bool budget_out = !is_help && !(hs & kHsHelped) && budget - kWave * g.L <= 0;  // (with helpers: no yield)
-        bool ends_nocand = false;  // no candidate in this tile => the stream is finished
-        if (!is_help && last_of_region) {
-            const int64_t s2 = cur.s + mx - 1 <= cur.n - 1 ? cur.s + mx : cur.n;
-            ends_nocand = s2 >= cur.n || s2 + static_cast<int64_t>(a.min_size) - 1 >= cur.n;
-        }
-        // The visit's last tile (absent a candidate): take the next ticket now, and reserve
-        // this stream's entry too when it will be yielded -- one atomic, hidden by the DMAs.
-        const bool switching = !is_help && (budget_out || ends_nocand);
-        const bool reserve = budget_out && !ends_nocand;
-        const bool claim_next = claim_next_r && !switching;  // a yielding owner claims nothing more
-        uint64_t ht_raw = 0;
-        if (switching) ht_raw = qht_add(a, lane, 1);  // the next stream's ticket
+        Tile tile = visit_tile(a, lane, me, v, is_help, hi, kWave * g.L, kWave * static_cast<int64_t>(a.lane_cap));
+        const int64_t ct = tile.ct, ct_next = tile.ct_next;
+        const bool last_of_region = tile.last_of_region, switching = tile.switching, claim_next = tile.claim_next;
         // Lane positions as 32-bit offsets from the tile start (a tile < 2^31 bytes): 64-bit
         // per-lane values live across the hash loop cost VGPRs this kernel does not have.
         const int32_t cl0 = lane * static_cast<int32_t>(g.L);
         const int32_t hi_rel = static_cast<int32_t>(hi - ct < 0x7FFFFFFF ? hi - ct : 0x7FFFFFFF);
-        uint32_t ht_lo = static_cast<uint32_t>(ht_raw), ht_hi = static_cast<uint32_t>(ht_raw >> 32);
+        uint32_t ht_lo = static_cast<uint32_t>(tile.ht_raw), ht_hi = static_cast<uint32_t>(tile.ht_raw >> 32);
         {
             uint32_t w16[16];
             __builtin_amdgcn_sched_barrier(0);
@@ -1636,19 +1828,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             hash.clear();
             hash.template block<kWarm>(w16);
         }
-        uint32_t tk = 0;
-        int64_t nbacklog = 0;
-        if (switching) {
-            const uint64_t ht = qht_value(ht_lo, ht_hi);
-            tk = static_cast<uint32_t>(ht);
-            nbacklog = static_cast<int64_t>(ht >> 32) + (reserve ? 1 : 0) - static_cast<int64_t>(tk) - 1;
-        }
-        uint64_t pe_raw = 0;
-        bool res_issued = false;
-        int nstate = 0;  // 0: next stream unresolved, 2: resolved, 3: + its first tile prefetched
-        PStream nx;
-        nx.ct = -1;
-        bool next_issued = false;
+        tile.set_ticket(ht_lo, ht_hi);
         int32_t found = -1;  // offset from ct of this lane's first candidate
         const int poll_step = g.nb > 1 ? g.nb / 2 : 0;
         // The owner's claim on tile htile + 1: an atomic add on its slot's bottom in step 0 (no
@@ -1656,13 +1836,6 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
         // LDS-DMA into the idle warm slot in step 1 (behind step 1's wait, which the add has
         // passed) and looked at in the last step, before the next tile's prefetch.  One- and
         // two-step tiles read it at the tile end (and prefetch nothing).
-        bool claim_ok = false, claim_known = !claim_next;
-        auto claim_decode = [&](uint64_t cw) {  // cw: the claim word after this tile's add
-            const uint32_t top = static_cast<uint32_t>(cw >> 20) & 0xFFFFFu, bot = static_cast<uint32_t>(cw) & 0xFFFFFu;
-            claim_ok = static_cast<uint32_t>(cw >> 40) == hep && bot <= top;
-            if (top < hK()) hs |= kHsHelped;
-            claim_known = true;
-        };
         for (int n = 0; n < g.nb; n++) {
             const int32_t cl = cl0 + 128 * n;
             const uint32_t st0 = hash.save();
@@ -1670,22 +1843,19 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             read_step128h(sl, lane, ct == 0 && cl == 0, cur.off0, dw);
-            if (claim_next && n >= 2 && n == g.nb - 1) claim_decode(*reinterpret_cast<const uint64_t*>(wl));
+            if (claim_next && n >= 2 && n == g.nb - 1) tile.claim_decode(v, *reinterpret_cast<const uint64_t*>(wl));
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slot free: refill it
             __builtin_amdgcn_sched_barrier(0);
 
-            if (reserve && n == g.nb - 1) {  // this stream's entry, reserved late
-                pe_raw = qht_add(a, lane, 1ull << 32);
-                res_issued = true;
-            }
+            if (tile.reserve && n == g.nb - 1) tile.reserve_entry(a, lane);  // this stream's entry, reserved late
             if (switching && n == poll_step) {
-                pentry_dma(a, lane, tk, wl32);
+                pentry_dma(a, lane, tile.tk, wl32);
                 if (n == g.nb - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing to hide it under
             }
             if (claim_next && n == 1) help_claim_dma(a, lane, me, wl32);
             if (n + 1 < g.nb) {
                 dma_step128(g.ld, g.ld.tb, sl32, ct, g.L, n + 1, lane);
-            } else if (!switching && !last_of_region && claim_known && (!claim_next || claim_ok) &&
+            } else if (!switching && !last_of_region && tile.claim_known && (!claim_next || tile.claim_ok) &&
                        __ballot(found >= 0) == 0) {
                 // (a candidate in an earlier step means the region's cut is in this tile: the
                 // next tile would be a stale prefetch, 12 KiB of HBM traffic per chunk wasted --
@@ -1693,7 +1863,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
                 PStream t2 = cur;  // next tile of this region (ours)
                 t2.ct = ct_next;
                 ptile_issue(t2, hi, wl32, sl32, lane, lcap);
-                next_issued = true;
+                tile.next_issued = true;
             }
             if (claim_next && n == 0 && lane == 0)
                 __hip_atomic_fetch_add((gu64*)help_claim(a, me), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1715,154 +1885,36 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             }
         }
         // ---- end of tile
-        if (!claim_known) {  // a one- or two-step tile: its claim is read here
+        if (!tile.claim_known) {  // a one- or two-step tile: its claim is read here
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (g.nb == 2) {
-                claim_decode(*reinterpret_cast<const uint64_t*>(wl));
+                tile.claim_decode(v, *reinterpret_cast<const uint64_t*>(wl));
             } else {
                 const uint64_t raw = ld_agent64(help_claim(a, me));
-                claim_decode(qht_value(static_cast<uint32_t>(raw), static_cast<uint32_t>(raw >> 32)));
+                tile.claim_decode(v, qht_value(static_cast<uint32_t>(raw), static_cast<uint32_t>(raw >> 32)));
             }
-        }
-        if (reserve && !res_issued) {
-            pe_raw = qht_add(a, lane, 1ull << 32);
-            res_issued = true;
         }
         const uint64_t hit = __ballot(found >= 0);
 #if KCDC_TRACE
         if (is_help) tr_help_t += __builtin_amdgcn_s_memrealtime() - tr_t0;
         else tr_own_end = __builtin_amdgcn_s_memrealtime();
 #endif
-        if (is_help) {
-            bool done = true;
-            if (hit || last_of_region) {  // post the tile's first candidate to its owner's row
-                int64_t f = -1;
-                if (hit) f = ct + __builtin_amdgcn_readfirstlane(__shfl(found, __builtin_ctzll(hit)));
-                help_post(a, lane, static_cast<uint32_t>(cur.cb), cur.epoch, static_cast<uint32_t>(cur.cnt), cur.s, f);
-            } else {  // the next sub-tile (prefetched), unless the owner has closed the region
-                const uint64_t w = ld_agent64(help_claim(a, static_cast<uint32_t>(cur.cb)));
-                done = static_cast<uint32_t>(qht_value(static_cast<uint32_t>(w), static_cast<uint32_t>(w >> 32)) >> 40) !=
-                       cur.epoch;
-            }
-            if (!done) {
-                cur.ct = ct_next;
-                issued = next_issued;
-                continue;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the post, or a dropped prefetch
-            need_take = true;
-            take_t = held_get(a, lane, me, static_cast<uint32_t>(cur.cap));
-            take_backlog = 0;
-            take_claim = 0xFFFFFFFFu;
-            continue;
-        }
-        bool region_changed = true;
-        const int64_t forced = cur.s + mx - 1 <= cur.n - 1 ? cur.s + mx : cur.n;  // max-size cut / the end
-        int64_t cut = -1;  // this region's cut, once known
-        if (hit) {
-            const int64_t f = ct + __builtin_amdgcn_readfirstlane(__shfl(found, __builtin_ctzll(hit)));
-            cut = f - cur.off0 + 1;
-        } else if (last_of_region) {  // forced cut at max size (splitter_buzhash32.go:60-64) or the end
-            cut = forced;
-        } else if (claim_next && !claim_ok) {  // the helpers hold the rest of the region
-            const int64_t T = kWave * static_cast<int64_t>(a.lane_cap);
-            const int64_t ct0 = ct - static_cast<int64_t>(htile()) * T;  // the published tile 0
-            const int64_t r = help_wait(a, lane, me, hep, htile() + 1u, hK(), ct0);
-            const int64_t wend = ct0 + static_cast<int64_t>(hK()) * T;  // past the published window
-            if (r >= 0) {
-                cut = r - cur.off0 + 1;
-            } else if (r == -1 && wend <= hi) {  // no candidate in the window: publish the next one
-                cur.ct = wend;
-                help_close(a, lane, me, hep);
-                hs = kHsNeedPub;
-                region_changed = false;
-            } else if (r == -1) {
-                cut = forced;
-            } else {  // a tile still pending: scan on from it, unshared
-                cur.ct = ct0 + (-2 - r) * T;
-                help_close(a, lane, me, hep);
-                hs = 0;
-                region_changed = false;
-            }
-        } else {
-            cur.ct = ct_next;
-            hs += 1u << 8;  // htile++
-            budget -= kWave * g.L;
-            region_changed = false;
-            if ((hs & kHsPub) && htile() >= hK()) {  // past its published window: the next one
-                help_close(a, lane, me, hep);
-                hs = kHsNeedPub;
-            }
-        }
-        if (cut >= 0) {
-            emit_cut(a, cur, lane, cut);
-            cur.s = cut;
-            cur.ct = -1;
-        }
-        if (region_changed) {
-            if (hs & kHsPub) help_close(a, lane, me, hep);
-            hs = kHsNeedPub;
-        }
-        const bool live = pstream_region(a, cur, lane);
-        if (!live && lane == 0) {
-            a.counts[cur.sid] = cur.cnt;
-            add_agent(a.queue + kQDone, 1u);
-        }
-        if (!switching && live) {  // same stream, next tile
-            issued = next_issued && !region_changed;
-            if (next_issued && region_changed) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stale prefetch
-            continue;
-        }
-        // ---- switch streams: requeue this one first (its reserve atomic was issued in the
-        // last step, so no prefetch DMA is in flight behind it), then prefetch the next
-        if (hs & kHsPub) help_close(a, lane, me, hep);  // a yielded region is not ours to share any more
-        hs = kHsNeedPub;
-        if (reserve) {
-            const uint32_t pe = static_cast<uint32_t>(
-                qht_value(static_cast<uint32_t>(pe_raw), static_cast<uint32_t>(pe_raw >> 32)) >> 32);
-            pwrite(a, lane, pe, cur, !live);
-        } else if (live) {  // a candidate kept the stream alive past its predicted last tile
-            const uint64_t ht = qht_take(a, lane, 1ull << 32);
-            pwrite(a, lane, static_cast<uint32_t>(ht >> 32), cur, false);
-        }
-        if (switching) {  // next stream: its entry landed in the warm slot (the last step's wait drained it)
-            const u32x4 ev = *reinterpret_cast<const u32x4*>(wl + 16 * (lane & 7));
-            if (pentry_ok(ev, lane, tk) && static_cast<uint32_t>(__builtin_amdgcn_readlane(ev.w, 0)) != kTombstone) {
-                pentry_decode(nx, ev);
-                uniformize(nx);
-                if (!pcheck(a, lane, nx, tk, 2)) return;
-                nstate = 2;
-                if (nx.ct < 0 && nx.s < nx.n && nx.s + static_cast<int64_t>(a.min_size) - 1 < nx.n)
-                    nx.ct = (nx.s + static_cast<int64_t>(a.min_size) - 1 + nx.off0) & ~int64_t(127);
-                if (nx.ct >= 0) {  // prefetch its first tile now, under this tile's bookkeeping
-                    int64_t nlo, nhi;
-                    pregion(a, nx, nlo, nhi);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // entry read before the slot refill
-                    ptile_issue(nx, nhi, wl32, sl32, lane, a.lane_cap);
-                    nstate = 3;
-                }
-            }
-        }
-        if (nstate >= 2) {
-            cur = nx;
-            issued = nstate == 3;
-            budget = pipe_quantum_tiles(nbacklog, a.lane_cap);
-            if (pstream_region(a, cur, lane)) continue;
-            if (lane == 0) {  // nothing left to scan in it
-                a.counts[cur.sid] = cur.cnt;
-                add_agent(a.queue + kQDone, 1u);
-            }
-            need_take = true;
-            take_t = 0xFFFFFFFFu;
-            take_backlog = 0;
-            take_claim = 0xFFFFFFFFu;
-            continue;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no prefetch may remain in flight
-        need_take = true;
-        take_t = switching ? tk : 0xFFFFFFFFu;
-        take_backlog = nbacklog;
-        take_claim = 0xFFFFFFFFu;
+        // the tile's first candidate (coordinate), or -1
+        const int64_t f = hit ? ct + __builtin_amdgcn_readfirstlane(__shfl(found, __builtin_ctzll(hit))) : -1;
+        if (visit_resolve(a, lane, me, v, tile, f, kWave * static_cast<int64_t>(a.lane_cap))) continue;
+        // ---- switch streams: the next one's entry landed in the warm slot (the last step's wait
+        // drained it); prefetch its first tile now, under this tile's bookkeeping
+        const auto prefetch = [&](PStream& nx) {
+            if (nx.ct < 0 && nx.s < nx.n && nx.s + static_cast<int64_t>(a.min_size) - 1 < nx.n)
+                nx.ct = (nx.s + static_cast<int64_t>(a.min_size) - 1 + nx.off0) & ~int64_t(127);
+            if (nx.ct < 0) return false;
+            int64_t nlo, nhi;
+            pregion(a, nx, nlo, nhi);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // entry read before the slot refill
+            ptile_issue(nx, nhi, wl32, sl32, lane, a.lane_cap);
+            return true;
+        };
+        if (!visit_adopt(a, lane, v, wl, switching, switching ? tile.tk : 0xFFFFFFFFu, tile.nbacklog, quantum, prefetch)) KCDC_PRET;
     }
 }
 
@@ -2256,6 +2308,13 @@ constexpr int64_t kRkLaneMul = 2;
 // Intra-region help as in split_batch_pipe_kernel (the same help slots, claim words and rows; hep,
 // hs and the kHs* flags mean the same).  An own tile is T = 64 x rk_cap bytes; a help task scans
 // one in two sub-tiles of rk_cap / 2 bytes per lane.
+// This kernel spells the visit protocol out itself, statement for statement what Visit, Tile and
+// the visit_* functions above do for the buzhash kernel: on the shared functions it measured
+// slower (same-process A/B against the kernel as it stands, 4M: 4096 x 4 MiB 2.221 vs 2.205 ms,
+// 1024 x 16 MiB 4.092 vs 4.031, 512 x 32 MiB 6.512 vs 6.381; with only the take and the adoption
+// shared, 512 x 32 MiB 6.406 and 128K 64 x 64 MiB 29.66 vs 29.42).  The statements are the same;
+// the register allocation around the walk is not (200 vs 185 SGPR spills, 50 vs 35 spill reloads
+// in the walk's blocks).  A change to the protocol is made in both places.
 __global__ __launch_bounds__(kRkWaves * kWave, kRkWaves / 4) void split_batch_rk_kernel(BatchArgs a) {
     __shared__ RkTables smt;
     __shared__ RkSlots smslots;
@@ -2296,7 +2355,6 @@ __global__ __launch_bounds__(kRkWaves * kWave, kRkWaves / 4) void split_batch_rk
     PStream cur;
     int64_t budget = kNoYield;
     uint32_t hep = 0, hs = 0;
-    constexpr uint32_t kHsPub = 1u << 16, kHsNeedPub = 1u << 17, kHsHelped = 1u << 18;
     hs = kHsNeedPub;
     auto hK = [&] { return hs & 0xFFu; };
     auto htile = [&] { return (hs >> 8) & 0xFFu; };
@@ -2393,7 +2451,7 @@ __global__ __launch_bounds__(kRkWaves * kWave, kRkWaves / 4) void split_batch_rk
             const int64_t T = kWave * rk_cap;
             const uint32_t K = static_cast<uint32_t>((hi - ct + T) / T);
             hs = 0;
-            if (a.help && help_phase(budget) && K >= kHelpMinTiles && K <= static_cast<uint32_t>(kHelpTiles)) {
+            if (a.help && K >= kHelpMinTiles && K <= static_cast<uint32_t>(kHelpTiles)) {
                 const uint32_t Kw = a.help_window && K > a.help_window ? a.help_window : K;  // a window
                 hep++;
                 hs = kHsPub | Kw;
@@ -3621,7 +3679,7 @@ struct TestKnobs {
     bool force_error = false;  // mark every pipelined launch as failed
     int help = 0;              // intra-region help: 0 the policy below, 1 off, 2 on (A/B, tests)
     uint32_t lane_cap = 0;     // buzhash batch lane segment cap (256..4096, a power of two); 0: base_args' rule
-    uint32_t help_window = 0;  // buzhash help window in tiles (255: whole regions); 0: launch_split_batch's rule
+    uint32_t help_window = 0;  // both batch kernels' help window in tiles (255: whole regions); 0: batch_plan's rule
     char* last_ws = nullptr;   // queue header of the last pipelined launch (kcdc_test_queue_stat)
     int last_dev = 0;
     uint32_t last_waves = 0;   // launch waves of that launch (kcdc_test_queue_stat key 12)
@@ -3647,6 +3705,14 @@ BuzFrame buz_frame(uint32_t mask) {
     return f;
 }
 
+uint32_t base_lane_cap(const Algo& algo, const TestKnobs& knobs) {
+    // largest power of two <= avg / 256, within [256, kLaneMax]: tiles of ~avg/4 (1 MiB and
+    // larger averages keep the full 2 KiB lane segments)
+    uint64_t cap = algo.kind == kBuzhash ? dev::kBuzLaneMax : dev::kLaneMax;
+    while (cap > 256 && cap * dev::kTileDiv > algo.avg) cap >>= 1;
+    return algo.kind == kBuzhash && knobs.lane_cap ? knobs.lane_cap : static_cast<uint32_t>(cap);
+}
+
 dev::BatchArgs base_args(const Algo& algo, const DeviceTables& t) {
     dev::BatchArgs a{};
     a.min_size = algo.min_size();
@@ -3662,11 +3728,7 @@ dev::BatchArgs base_args(const Algo& algo, const DeviceTables& t) {
     a.rk_out = t.rk_out;
     a.rk_mod = t.rk_mod;
     a.rk_shift = static_cast<uint32_t>(tables().rk_shift);
-    // largest power of two <= avg / 256, within [256, kLaneMax]: tiles of ~avg/4 (1 MiB and
-    // larger averages keep the full 2 KiB lane segments)
-    uint64_t cap = algo.kind == kBuzhash ? dev::kBuzLaneMax : dev::kLaneMax;
-    while (cap > 256 && cap * dev::kTileDiv > algo.avg) cap >>= 1;
-    a.lane_cap = algo.kind == kBuzhash && g_test.lane_cap ? g_test.lane_cap : static_cast<uint32_t>(cap);
+    a.lane_cap = base_lane_cap(algo, g_test);
     return a;
 }
 #if KCDC_TRACE || KCDC_DEBUG_CHECKS
@@ -3741,6 +3803,147 @@ const DeviceTables* device_tables(int device, int* err) {
     return &g_dev_tables[device];
 }
 
+namespace {
+// What a pipelined batch launch runs with: a pure function of the splitter, the stream count, the
+// device's CUs and the test knobs.
+struct BatchPlan {
+    bool helpers;          // waiting waves help scan the owners' regions
+    unsigned grid;         // workgroups (persistent: at most one per CU)
+    unsigned wg_waves;     // waves per workgroup
+    uint32_t lane_cap;     // BatchArgs::lane_cap
+    uint32_t help_window;  // BatchArgs::help_window
+    uint64_t ring;         // ring entries (a power of two)
+    uint32_t hwaves;       // help slots: one per launch wave, none without helpers
+    size_t ring_bytes, bytes;  // the ring's bytes; the whole workspace: header | ring | help area
+};
+BatchPlan batch_plan(const Algo& algo, uint32_t nstreams, unsigned cus, const TestKnobs& knobs) {
+    BatchPlan p{};
+    p.lane_cap = base_lane_cap(algo, knobs);
+    const unsigned wg_waves = algo.kind == kRabinKarp ? dev::kRkWaves : dev::kDmaWaves;
+    const unsigned need = (nstreams + wg_waves - 1) / wg_waves;
+    // With helpers the batch kernels take the whole chip even for a few streams: the waves
+    // without a stream help scan the owners' regions (help slots).  Help pays when a chunk's
+    // test region spans many tiles: averages of 1 MiB and up (12+ buzhash tiles, 6+ Rabin-Karp
+    // tiles per region).  Below that, the claims, row waits and helpers' polling cost more than
+    // the tail they remove (same-process A/B, 4096 x 4 MiB: 128K-BUZHASH 3.42 vs 3.13 ms with
+    // help off, 512K 2.37 vs 2.27; 64 x 64 MiB 128K-BUZHASH 27.5 vs 22.2 ms), except for the
+    // Rabin-Karp kernel in launches with fewer streams than waves (64 x 64 MiB 128K-RABINKARP
+    // 30.1 vs 38.0 ms); DESIGN.md §2.1d, profiles/r05/help_policy/.
+    const bool helpers = knobs.help == 2 ||
+                         (knobs.help == 0 &&
+                          (algo.avg >= dev::kHelpMinAvg ||
+                           (algo.kind == kRabinKarp && nstreams < static_cast<uint64_t>(cus) * wg_waves)));
+    unsigned grid = helpers || need >= cus ? cus : need;
+    if (grid > dev::kMaxPipeGrid) grid = dev::kMaxPipeGrid;  // one claim flag per workgroup
+    // Fewer streams than waves: the waves without a stream of their own live on help tasks
+    // (half tiles of the owners' regions), and 4 KiB buzhash lanes (tiles and help tasks twice
+    // as long, half the claims, posts and warm-ups per region) win there, while with more
+    // streams than waves they lose (the coarser tail).  Same-process A/B,
+    // bit-exact, 2 KiB -> 4 KiB (profiles/r06/lane4k/): 4M 2048 x 8 MiB 1.864 -> 1.753 ms,
+    // 1024 x 16 MiB 2.855 -> 2.516, 512 x 32 MiB 9.72 -> 7.69; 2M 1024 x 16 MiB 3.09 -> 2.84;
+    // 1M loses at 2048 x 8 MiB (2.22 -> 2.29) and gains from 1024 x 16 MiB on (3.67 -> 3.61).
+    if (algo.kind == kBuzhash && !knobs.lane_cap && p.lane_cap == dev::kBuzLaneMax && helpers &&
+        nstreams * (algo.avg >= (2u << 20) ? 1u : 2u) <= static_cast<uint64_t>(grid) * wg_waves)
+        p.lane_cap = 2 * dev::kBuzLaneMax;
+    // Four or more waves per stream (both batch kernels): helpers outnumber the owners, and regions published
+    // four tiles at a time keep them just ahead of the owner instead of on the far end of the
+    // region (512 x 32 MiB 4M 7.83 -> 5.89 ms, 1M 8.28 -> 6.93).  With one helper per owner the
+    // windows' re-publishing costs more than they save (1024 x 16 MiB 4M 2.49 -> 2.58 at 8
+    // tiles, 3.10 at 4), so whole regions stay published there (profiles/r06/help_window/).
+    if (knobs.help_window)
+        p.help_window = knobs.help_window == 255u ? 0u : knobs.help_window;
+    else if (helpers && 4u * nstreams <= static_cast<uint64_t>(grid) * wg_waves) {
+        // buzhash: wider windows for more helpers per owner (16 waves per stream, 128 x 128 MiB:
+        // W = 4 19.9 ms, 6 17.3, 8 18.8; 32 per stream, 64 x 256 MiB: 4 33.4, 6 30.4, 8 27.9)
+        const uint64_t wps = static_cast<uint64_t>(grid) * wg_waves / nstreams;
+        p.help_window = algo.kind == kBuzhash && wps >= 32 ? 8u : algo.kind == kBuzhash && wps >= 16 ? 6u : 4u;
+    }
+    // Rabin-Karp (a tile is ~2.5x a buzhash tile's time, so re-publishing costs relatively
+    // less): windows of 8 tiles pay from one helper per owner on (1024 x 16 MiB 4M 4.52 ->
+    // 4.05 ms, 1M 5.56 -> 5.46); with four or more, 4 tiles (512 x 32 MiB 8.17 -> 6.33,
+    // 256 x 64 MiB 19.06 -> 11.69; profiles/r06/help_window/rk/)
+    else if (algo.kind == kRabinKarp && helpers && 2u * nstreams <= static_cast<uint64_t>(grid) * wg_waves)
+        p.help_window = 8u;
+    uint64_t ring = 1;
+    // every push (yields, tombstones) takes a fresh slot; a launch pushes at most
+    // a few entries per wave beyond the initial n: size the ring with ample margin
+    const uint64_t live = static_cast<uint64_t>(nstreams) + 8ull * grid * wg_waves;
+    while (ring <= live) ring <<= 1;
+    const size_t ring_bytes = static_cast<size_t>(dev::kPEntryStride) * ring;
+    const uint32_t hwaves = helpers ? grid * wg_waves : 0u;
+    const size_t help_bytes = static_cast<size_t>(hwaves) * (128u + 64u + 8u * dev::kHelpTiles) + 4u * ((hwaves + 31u) / 32u);
+    p.helpers = helpers;
+    p.grid = grid;
+    p.wg_waves = wg_waves;
+    p.ring = ring;
+    p.hwaves = hwaves;
+    p.ring_bytes = ring_bytes;
+    p.bytes = dev::kQHeaderBytes + ring_bytes + help_bytes;
+    return p;
+}
+
+// The queue workspace slot of a launch on stream st, with at least `bytes` bytes; call with
+// g_dev_mu[device] held.  The slot is chosen by stream affinity (see StreamSlot) and grown
+// stream-ordered; a launch that takes over a slot from another stream waits for the slot's
+// last launch.
+int queue_slot(int device, hipStream_t st, size_t bytes, QueueWs*& out) {
+    unsigned slot = kQueueSlots;
+    StreamSlot* aff = nullptr;
+    for (StreamSlot& e : g_stream_slot[device]) {
+        if (e.valid && e.st == st) aff = &e;
+    }
+    if (aff && g_qws[device][aff->slot].last == st) slot = aff->slot;
+    if (slot == kQueueSlots) {
+        slot = g_queue_next[device]++ % kQueueSlots;
+        if (!aff) {  // remember this stream in the least recently used entry
+            aff = &g_stream_slot[device][0];
+            for (StreamSlot& e : g_stream_slot[device])
+                if (!e.valid || e.tick < aff->tick) aff = &e;
+            aff->valid = true;
+            aff->st = st;
+        }
+        aff->slot = slot;
+    }
+    aff->tick = ++g_slot_tick[device];
+    QueueWs& q = g_qws[device][slot];
+    const bool same_stream = q.used && q.last == st;  // stream order covers the previous launch
+    if (q.bytes < bytes) {
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+        char* nb = nullptr;
+        size_t nbytes = bytes > 2 * q.bytes ? bytes : 2 * q.bytes;
+        // Stream-ordered: a plain hipFree synchronises the whole device, so a launch that
+        // grows its slot would wait for every kernel on every stream (tests/test_gpu_queue.py
+        // steal test: the batch waited out a 300 ms occupier on another stream).
+        hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&nb), nbytes, st);
+        if (e == hipSuccess && q.base) {  // the slot's previous launches are the old buffer's only users
+            if (q.done) e = hipStreamWaitEvent(st, q.done, 0);
+            if (e == hipSuccess) e = hipFreeAsync(q.base, st);
+        }
+        (void)hipSetDevice(prev);
+        if (e != hipSuccess) return hip_fail(e, "queue workspace");
+        q.base = nb;
+        q.bytes = nbytes;
+    }
+    if (!q.done) {
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+        const hipError_t e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming | hipEventDisableSystemFence);
+        (void)hipSetDevice(prev);
+        if (e != hipSuccess) return hip_fail(e, "queue workspace event");
+    } else if (!same_stream) {
+        const hipError_t e = hipStreamWaitEvent(st, q.done, 0);
+        if (e != hipSuccess) return hip_fail(e, "queue workspace wait");
+    }
+    q.last = st;
+    q.used = true;
+    out = &q;
+    return 0;
+}
+}  // namespace
+
 int launch_split_batch(const Algo& algo, const SplitArgs& s, int device, void* stream) {
     int err = 0;
     const DeviceTables* t = device_tables(device, &err);
@@ -3762,166 +3965,51 @@ int launch_split_batch(const Algo& algo, const SplitArgs& s, int device, void* s
     if (algo.kind == kFixed) {
         hipLaunchKernelGGL(dev::split_fixed_kernel, dim3(s.nstreams), dim3(256), 0, st, a);
     } else {
-        const unsigned cus = static_cast<unsigned>(t->cus);
         if (algo.kind == kRabinKarp && tables().rk_shift != 45)
             return set_error(-22, "Rabin-Karp kernel: the polynomial must have degree 53");
-        const unsigned wg_waves = algo.kind == kRabinKarp ? dev::kRkWaves : dev::kDmaWaves;
-        const unsigned need = (s.nstreams + wg_waves - 1) / wg_waves;
-        // With helpers the batch kernels take the whole chip even for a few streams: the waves
-        // without a stream help scan the owners' regions (help slots).  Help pays when a chunk's
-        // test region spans many tiles: averages of 1 MiB and up (12+ buzhash tiles, 6+ Rabin-Karp
-        // tiles per region).  Below that, the claims, row waits and helpers' polling cost more than
-        // the tail they remove (same-process A/B, 4096 x 4 MiB: 128K-BUZHASH 3.42 vs 3.13 ms with
-        // help off, 512K 2.37 vs 2.27; 64 x 64 MiB 128K-BUZHASH 27.5 vs 22.2 ms), except for the
-        // Rabin-Karp kernel in launches with fewer streams than waves (64 x 64 MiB 128K-RABINKARP
-        // 30.1 vs 38.0 ms); DESIGN.md §2.1d, profiles/r05/help_policy/.
-        const bool helpers = g_test.help == 2 ||
-                             (g_test.help == 0 &&
-                              (algo.avg >= KCDC_HELP_MIN_AVG ||
-                               (algo.kind == kRabinKarp && s.nstreams < static_cast<uint64_t>(cus) * wg_waves)));
-        unsigned grid = helpers || need >= cus ? cus : need;
-        if (grid > dev::kMaxPipeGrid) grid = dev::kMaxPipeGrid;  // one claim flag per workgroup
-        // Fewer streams than waves: the waves without a stream of their own live on help tasks
-        // (half tiles of the owners' regions), and 4 KiB buzhash lanes (tiles and help tasks twice
-        // as long, half the claims, posts and warm-ups per region) win there, while with more
-        // streams than waves they lose (the coarser tail).  Same-process A/B,
-        // bit-exact, 2 KiB -> 4 KiB (profiles/r06/lane4k/): 4M 2048 x 8 MiB 1.864 -> 1.753 ms,
-        // 1024 x 16 MiB 2.855 -> 2.516, 512 x 32 MiB 9.72 -> 7.69; 2M 1024 x 16 MiB 3.09 -> 2.84;
-        // 1M loses at 2048 x 8 MiB (2.22 -> 2.29) and gains from 1024 x 16 MiB on (3.67 -> 3.61).
-        if (algo.kind == kBuzhash && !g_test.lane_cap && a.lane_cap == dev::kBuzLaneMax && helpers &&
-            s.nstreams * (algo.avg >= (2u << 20) ? 1u : 2u) <= static_cast<uint64_t>(grid) * wg_waves)
-            a.lane_cap = 2 * dev::kBuzLaneMax;
-        // Four or more waves per stream (both batch kernels): helpers outnumber the owners, and regions published
-        // four tiles at a time keep them just ahead of the owner instead of on the far end of the
-        // region (512 x 32 MiB 4M 7.83 -> 5.89 ms, 1M 8.28 -> 6.93).  With one helper per owner the
-        // windows' re-publishing costs more than they save (1024 x 16 MiB 4M 2.49 -> 2.58 at 8
-        // tiles, 3.10 at 4), so whole regions stay published there (profiles/r06/help_window/).
-        if (g_test.help_window)
-            a.help_window = g_test.help_window == 255u ? 0u : g_test.help_window;
-        else if (helpers && 4u * s.nstreams <= static_cast<uint64_t>(grid) * wg_waves) {
-            // buzhash: wider windows for more helpers per owner (16 waves per stream, 128 x 128 MiB:
-            // W = 4 19.9 ms, 6 17.3, 8 18.8; 32 per stream, 64 x 256 MiB: 4 33.4, 6 30.4, 8 27.9)
-            const uint64_t wps = static_cast<uint64_t>(grid) * wg_waves / s.nstreams;
-            a.help_window = algo.kind == kBuzhash && wps >= 32 ? 8u : algo.kind == kBuzhash && wps >= 16 ? 6u : 4u;
-        }
-        // Rabin-Karp (a tile is ~2.5x a buzhash tile's time, so re-publishing costs relatively
-        // less): windows of 8 tiles pay from one helper per owner on (1024 x 16 MiB 4M 4.52 ->
-        // 4.05 ms, 1M 5.56 -> 5.46); with four or more, 4 tiles (512 x 32 MiB 8.17 -> 6.33,
-        // 256 x 64 MiB 19.06 -> 11.69; profiles/r06/help_window/rk/)
-        else if (algo.kind == kRabinKarp && helpers && 2u * s.nstreams <= static_cast<uint64_t>(grid) * wg_waves)
-            a.help_window = 8u;
-        uint64_t ring = 1;
-        // every push (yields, tombstones) takes a fresh slot; a launch pushes at most
-        // a few entries per wave beyond the initial n: size the ring with ample margin
-        const uint64_t live = static_cast<uint64_t>(s.nstreams) + 8ull * grid * wg_waves;
-        while (ring <= live) ring <<= 1;
-        const size_t ring_bytes = static_cast<size_t>(dev::kPEntryStride) * ring;
-        const size_t hdr = dev::kQHeaderBytes;
-        const uint32_t hwaves = helpers ? grid * wg_waves : 0u;
-        const size_t help_bytes = static_cast<size_t>(hwaves) * (128u + 64u + 8u * dev::kHelpTiles) + 4u * ((hwaves + 31u) / 32u);
-        const size_t bytes = hdr + ring_bytes + help_bytes;
-        char* ws = nullptr;
+        const BatchPlan p = batch_plan(algo, s.nstreams, static_cast<unsigned>(t->cus), g_test);
+        a.lane_cap = p.lane_cap;
+        a.help_window = p.help_window;
         // The slot stays locked from its selection to its event record, so a later user of the
         // same slot always waits for this launch.
         std::lock_guard<std::mutex> lk(g_dev_mu[device]);
-        unsigned slot = kQueueSlots;
-        StreamSlot* aff = nullptr;
-        for (StreamSlot& e : g_stream_slot[device]) {
-            if (e.valid && e.st == st) aff = &e;
-        }
-        if (aff && g_qws[device][aff->slot].last == st) slot = aff->slot;
-        if (slot == kQueueSlots) {
-            slot = g_queue_next[device]++ % kQueueSlots;
-            if (!aff) {  // remember this stream in the least recently used entry
-                aff = &g_stream_slot[device][0];
-                for (StreamSlot& e : g_stream_slot[device])
-                    if (!e.valid || e.tick < aff->tick) aff = &e;
-                aff->valid = true;
-                aff->st = st;
-            }
-            aff->slot = slot;
-        }
-        aff->tick = ++g_slot_tick[device];
-        QueueWs& q = g_qws[device][slot];
-        const bool same_stream = q.used && q.last == st;  // stream order covers the previous launch
-        {
-            if (q.bytes < bytes) {
-                int prev = 0;
-                (void)hipGetDevice(&prev);
-                (void)hipSetDevice(device);
-                char* nb = nullptr;
-                size_t nbytes = bytes > 2 * q.bytes ? bytes : 2 * q.bytes;
-                // Stream-ordered: a plain hipFree synchronises the whole device, so a launch that
-                // grows its slot would wait for every kernel on every stream (tests/test_gpu_queue.py
-                // steal test: the batch waited out a 300 ms occupier on another stream).
-                hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&nb), nbytes, st);
-                if (e == hipSuccess && q.base) {  // the slot's previous launches are the old buffer's only users
-                    if (q.done) e = hipStreamWaitEvent(st, q.done, 0);
-                    if (e == hipSuccess) e = hipFreeAsync(q.base, st);
-                }
-                (void)hipSetDevice(prev);
-                if (e != hipSuccess) return hip_fail(e, "queue workspace");
-                q.base = nb;
-                q.bytes = nbytes;
-            }
-            ws = q.base;
-            if (!q.done) {
-                int prev = 0;
-                (void)hipGetDevice(&prev);
-                (void)hipSetDevice(device);
-                const hipError_t e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming | hipEventDisableSystemFence);
-                (void)hipSetDevice(prev);
-                if (e != hipSuccess) return hip_fail(e, "queue workspace event");
-            } else if (!same_stream) {
-                const hipError_t e = hipStreamWaitEvent(st, q.done, 0);
-                if (e != hipSuccess) return hip_fail(e, "queue workspace wait");
-            }
-            q.last = st;
-            q.used = true;
-        }
+        QueueWs* q = nullptr;
+        if (const int qe = queue_slot(device, st, p.bytes, q)) return qe;
+        char* ws = q->base;
         a.queue = reinterpret_cast<uint32_t*>(ws);
         g_test.last_ws = ws;
         g_test.last_dev = device;
-        g_test.last_waves = grid * wg_waves;
+        g_test.last_waves = p.grid * p.wg_waves;
 #if KCDC_TRACE || KCDC_DEBUG_CHECKS
         g_last_ws = ws;
 #endif
-        a.ring = reinterpret_cast<uint32_t*>(ws + hdr);
-        a.help = helpers ? reinterpret_cast<uint64_t*>(ws + hdr + ring_bytes) : nullptr;
-        a.help_waves = hwaves;
-        a.ring_mask = static_cast<uint32_t>(ring - 1);
+        a.ring = reinterpret_cast<uint32_t*>(ws + dev::kQHeaderBytes);
+        a.help = p.helpers ? reinterpret_cast<uint64_t*>(ws + dev::kQHeaderBytes + p.ring_bytes) : nullptr;
+        a.help_waves = p.hwaves;
+        a.ring_mask = static_cast<uint32_t>(p.ring - 1);
 
 #if KCDC_TRACE
-        if (trace_reserve(std::max<uint64_t>(s.nstreams, 3ull * grid * wg_waves)) != 0) return set_error(-12, "trace buffer");
+        if (trace_reserve(std::max<uint64_t>(s.nstreams, 3ull * p.grid * p.wg_waves)) != 0) return set_error(-12, "trace buffer");
         a.trace = g_trace;
 #endif
         // header + ring zeroed per launch (the ring is also left empty by every finished launch)
         {
-            const uint32_t slots = static_cast<uint32_t>(ring);
-            const uint64_t threads = std::max<uint64_t>(std::max<uint64_t>(8ull * slots, dev::kQHeaderBytes / 4), hwaves);  // >= nstreams
+            const uint32_t slots = static_cast<uint32_t>(p.ring);
+            const uint64_t threads = std::max<uint64_t>(std::max<uint64_t>(8ull * slots, dev::kQHeaderBytes / 4), p.hwaves);  // >= nstreams
             hipLaunchKernelGGL(dev::init_ring_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, st, a,
-                               slots, grid * wg_waves, g_test.spin_cap ? g_test.spin_cap : dev::kSpinCap,
+                               slots, p.grid * p.wg_waves, g_test.spin_cap ? g_test.spin_cap : dev::kSpinCap,
                                g_test.no_steal ? 0u : dev::kStealSpins);
         }
         // persistent grid: one workgroup per CU, never more workgroups than the streams need
-        if (algo.kind == kRabinKarp) {
-            hipLaunchKernelGGL(dev::split_batch_rk_kernel, dim3(grid), dim3(dev::kRkWaves * dev::kWave), 0, st, a);
-            if (g_test.force_error)
-                hipLaunchKernelGGL(dev::poison_counts_kernel, dim3(std::min<unsigned>((s.nstreams + 255) / 256, 256u)),
-                                   dim3(256), 0, st, a);
-        } else {
-            const bool top = buz_frame(static_cast<uint32_t>(algo.mask())).top;
-            if (top)
-                hipLaunchKernelGGL(dev::split_batch_pipe_kernel<true>, dim3(grid), dim3(dev::kDmaWaves * dev::kWave), 0,
-                                   st, a);
-            else
-                hipLaunchKernelGGL(dev::split_batch_pipe_kernel<false>, dim3(grid), dim3(dev::kDmaWaves * dev::kWave), 0,
-                                   st, a);
-            if (g_test.force_error)  // test hook: report a failed launch (kcdc_test_set)
-                hipLaunchKernelGGL(dev::poison_counts_kernel, dim3(std::min<unsigned>((s.nstreams + 255) / 256, 256u)),
-                                   dim3(256), 0, st, a);
-        }
-        const hipError_t er = hipEventRecord(q.done, st);
+        void (*kernel)(dev::BatchArgs) = algo.kind == kRabinKarp ? dev::split_batch_rk_kernel
+                                         : buz_frame(static_cast<uint32_t>(algo.mask())).top
+                                             ? dev::split_batch_pipe_kernel<true>
+                                             : dev::split_batch_pipe_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.wg_waves * dev::kWave), 0, st, a);
+        if (g_test.force_error)  // test hook: report a failed launch (kcdc_test_set)
+            hipLaunchKernelGGL(dev::poison_counts_kernel, dim3(std::min<unsigned>((s.nstreams + 255) / 256, 256u)),
+                               dim3(256), 0, st, a);
+        const hipError_t er = hipEventRecord(q->done, st);
         if (er != hipSuccess) return hip_fail(er, "queue workspace record");
     }
     const hipError_t e = hipGetLastError();
@@ -4271,6 +4359,7 @@ extern "C" int kcdc_test_set(int32_t key, int64_t value) {
             g_test.lane_cap = static_cast<uint32_t>(value);
             return 0;
         case 9:                                                            // KCDC_TEST_HELP_WINDOW
+            static_assert(dev::kHelpMinTiles == 3, "the range in the error text below");
             if (value < 0 || (value != 0 && (value < static_cast<int64_t>(dev::kHelpMinTiles) || value > 255)))
                 return set_error(-22, "help window: 0 (policy), 255 (whole regions), or tiles in [3, 254]");
             g_test.help_window = static_cast<uint32_t>(value);

@@ -683,8 +683,8 @@ def random_launch(seed, kind="buz", mutations=(), window=None):
     grid x waves per workgroup (the persistent grid), streams against waves (fewer than, equal to,
     a few more, many more: the backlog that turns yields on), regions and tiles per stream (the
     average size / lane cap: tiles per region), steps per tile (nb_full: lane cap / 128 B), the
-    visit quantum in tiles (KCDC_QUANTUM_TILES), the smallest published region
-    (KCDC_HELP_MIN_TILES), the owner's wait bound (KCDC_HELP_WAIT_TICKS), help on or off (the
+    visit quantum in tiles (pipe_quantum_tiles' kTiles), the smallest published region
+    (kHelpMinTiles), the owner's wait bound (kHelpWaitTicks), help on or off (the
     per-name policy), a workgroup that starts late (another kernel holds its CU: try_steal), and
     the help window (BatchArgs::help_window: regions published a few tiles at a time; drawn from
     its own generator so the other draws of a seed stay as they were)."""

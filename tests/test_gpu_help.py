@@ -249,3 +249,36 @@ def test_forced_help_in_other_geometries(gpu, name, lane_cap):
             got = batch.read_cuts(b)
             bad = [i for i in range(ns) if got[i].tolist() != want[i]]
             assert not bad, f"launch {launch}: {len(bad)} streams differ, first {bad[:5]}"
+
+
+@pytest.mark.parametrize("window", [3, 4])
+@pytest.mark.parametrize("name", ["DYNAMIC-4M-BUZHASH", "DYNAMIC-4M-RABINKARP", "DYNAMIC-1M-BUZHASH"])
+def test_help_windows(gpu, name, window):
+    """Regions published a window of tiles at a time (KCDC_TEST_HELP_WINDOW): an owner that finds
+    no candidate in its window re-publishes the next one, either as it walks past the window's end
+    or after waiting for the helpers' posts.  Few long streams with 128 KiB buzhash tiles
+    (KCDC_TEST_LANE_CAP = 2048; Rabin-Karp tiles are 256 KiB), so regions span many windows.  The
+    inputs are checked to reach those paths: chunks whose cut lies in the third window or later,
+    and forced max-size cuts (every window of the region passed)."""
+    import torch
+    ns, L = 4, 24 << 20
+    data = torch.empty(ns * L, dtype=torch.uint8, device=gpu)
+    batch.fill_prng(data, L, ns, L, SEED, first_sid=500)
+    cuts, counts = coracle.split_prng_streams(name, SEED, np.arange(500, 500 + ns), L, nthreads=16)
+    mn, mx = coracle.min_size(name), int(_lib.lib().kcdc_max_segment_size(name.encode()))
+    T = (256 if "RABINKARP" in name else 128) << 10
+    far = forced = 0
+    for i in range(ns):
+        s = 0
+        for cut in cuts[i, :counts[i]].tolist():
+            if cut - s >= mn:  # (the stream's last chunk may be shorter: it has no test region)
+                far += (cut - 1 - ((s + mn - 1) & ~127)) // T >= 2 * window
+                forced += cut - s == mx
+            s = cut
+    assert far >= 8 and forced >= 1, (far, forced)
+    with knob(_lib.TEST_HELP_WINDOW, window), knob(_lib.TEST_LANE_CAP, 2048):
+        got, helps = _split(name, data, [i * L for i in range(ns)], [L] * ns, gpu)
+        giveups = _lib.lib().kcdc_test_queue_stat(_lib.STAT_GIVEUPS)
+    for i in range(ns):
+        assert got[i].tolist() == cuts[i, :counts[i]].tolist(), f"{name} stream {i}"
+    assert helps > 0 and giveups == 0
