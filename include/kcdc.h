@@ -255,7 +255,9 @@ int kcdc_lpt_assign(const uint64_t* lens, uint32_t nstreams, uint32_t ndev, uint
  * cut set is identical to one sequential pass (no Concatenate seams; cf.
  * snapshot/upload/upload.go:166-209, repo/object/object_manager.go:102-152).
  * `workspace` must hold kcdc_long_workspace_bytes(name, len) bytes of device
- * memory.  d_count receives the number of cuts written to d_cuts. */
+ * memory.  d_count always receives the TRUE number of chunks; entries beyond
+ * `cuts_cap` are not written, so d_count > cuts_cap signals overflow (the batch
+ * contract above). */
 size_t kcdc_long_workspace_bytes(const char* name, uint64_t len);
 int kcdc_split_long_device(const char* name, const uint8_t* d_data, uint64_t len, uint64_t* d_cuts, uint64_t cuts_cap,
                            uint64_t* d_count, void* workspace, size_t workspace_bytes, void* hip_stream);
@@ -413,6 +415,16 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
  *                         [256, 2048]).  Other tile geometries for the same cuts.
  *   KCDC_TEST_HELP_WINDOW both batch kernels: tiles of a region published to helpers at a time,
  *                         in [3, 254]; 255: whole regions; 0: the default (the launch's rule)
+ *   KCDC_TEST_PAR_NODE_CAP long-stream launches (and their workspace sizes): nodes of the parallel
+ *                         resolver's tables per launch, in [1, 2^20]; 0: the default (2^20).  A
+ *                         stream whose nodes do not fit resolves serially, with the same cuts.
+ *   KCDC_TEST_LONG_STAT   1: every long-stream launch records which resolver took each of its
+ *                         streams, for kcdc_test_long_stat
+ * kcdc_test_long_stat: after the last long-stream launch made with KCDC_TEST_LONG_STAT on has
+ * finished (synchronise first): KCDC_TEST_LONG_STREAMS, the streams of that launch, or
+ * KCDC_TEST_LONG_SERIAL, how many of them the serial resolver took (truncated segments, or no
+ * room in the node tables); the parallel resolver took the others.  Negative KCDC_E* code if no
+ * launch was recorded.
  * kcdc_test_occupy: occupy `nwg` CUs (one workgroup with all of the CU's LDS each) for
  * `usec` microseconds on `hip_stream`, e.g. to run a batch beside a kernel that holds CUs.
  * kcdc_test_queue_stat: after the last pipelined batch launch has finished (synchronise
@@ -433,7 +445,12 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
 #define KCDC_TEST_ID_RING 7
 #define KCDC_TEST_LANE_CAP 8
 #define KCDC_TEST_HELP_WINDOW 9
+#define KCDC_TEST_PAR_NODE_CAP 10
+#define KCDC_TEST_LONG_STAT 11
 int kcdc_test_set(int32_t key, int64_t value);
+#define KCDC_TEST_LONG_STREAMS 1
+#define KCDC_TEST_LONG_SERIAL 2
+int64_t kcdc_test_long_stat(int32_t key);
 int kcdc_test_occupy(uint32_t nwg, uint32_t usec, void* hip_stream);
 #define KCDC_TEST_STAT_GIVEUPS 1
 #define KCDC_TEST_STAT_DONE 2

@@ -35,6 +35,9 @@ TEST_SPIN_CAP, TEST_NO_STEAL, TEST_FORCE_ERROR, TEST_HASH_LANES, TEST_NO_SERVER,
 TEST_ID_RING = 7
 TEST_LANE_CAP = 8
 TEST_HELP_WINDOW = 9
+TEST_PAR_NODE_CAP = 10
+TEST_LONG_STAT = 11
+LONG_STREAMS, LONG_SERIAL = 1, 2  # kcdc_test_long_stat keys
 STAT_GIVEUPS, STAT_DONE, STAT_STEALS, STAT_HELPS, STAT_TICKET_AUDIT = 1, 2, 3, 4, 5
 STAT_TICKETS, STAT_ENTRIES, STAT_WAVES = 10, 11, 12
 
@@ -97,6 +100,7 @@ _SIGS = {
     "kcdc_test_set": (C.c_int, [C.c_int32, C.c_int64]),
     "kcdc_test_occupy": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "kcdc_test_queue_stat": (C.c_int64, [C.c_int32]),
+    "kcdc_test_long_stat": (C.c_int64, [C.c_int32]),
     "kcdc_test_ws_copy": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "kcdc_test_server_requests": (C.c_int64, []),
     "kcdc_hash_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),

@@ -3683,6 +3683,11 @@ struct TestKnobs {
     char* last_ws = nullptr;   // queue header of the last pipelined launch (kcdc_test_queue_stat)
     int last_dev = 0;
     uint32_t last_waves = 0;   // launch waves of that launch (kcdc_test_queue_stat key 12)
+    uint64_t par_node_cap = 0; // long path: parallel-resolver nodes per launch; 0: kParNodeCap
+    bool long_stat = false;    // long path: keep each launch's serial[] flags for kcdc_test_long_stat
+    uint32_t* long_serial = nullptr;  // pinned host copy of the last long-path launch's serial[]
+    uint32_t long_serial_cap = 0, long_streams = 0;
+    bool long_seen = false;
 };
 TestKnobs g_test;
 
@@ -4226,7 +4231,9 @@ LongLayout long_layout(int64_t nseg, uint32_t nstreams) {
     L.levels = 0;
     L.off_serial = L.off_forced = L.off_jump = o;
     {  // resolve_par_kernel for streams with complete candidate lists
-        L.node_cap = std::min<uint64_t>(static_cast<uint64_t>(ns) * dev::kSegK + 2ull * nstreams, kParNodeCap);
+        // (the test knob is read here, so the workspace size functions and the launch agree)
+        L.node_cap = std::min<uint64_t>(static_cast<uint64_t>(ns) * dev::kSegK + 2ull * nstreams,
+                                        g_test.par_node_cap ? g_test.par_node_cap : kParNodeCap);
         L.levels = 1;
         while ((uint64_t(1) << L.levels) <= L.node_cap) L.levels++;
         L.off_serial = o;
@@ -4332,7 +4339,26 @@ int launch_split_long_multi(const Algo& algo, uint32_t m, const uint8_t* const* 
     else
         hipLaunchKernelGGL(dev::resolve_kernel<kRabinKarp>, dim3(m), dim3(dev::kWave), 0, st, a, g, mn, mx);
     e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "long-stream kernel launch");
+    if (e != hipSuccess) return hip_fail(e, "long-stream kernel launch");
+    if (g_test.long_stat) {  // test hook: which resolver took each stream (kcdc_test_long_stat)
+        if (m > g_test.long_serial_cap) {
+            if (g_test.long_serial) {  // (an earlier launch's copy may still be in flight)
+                (void)hipDeviceSynchronize();
+                (void)hipHostFree(g_test.long_serial);
+            }
+            g_test.long_serial = nullptr;
+            g_test.long_serial_cap = 0;
+            e = hipHostMalloc(reinterpret_cast<void**>(&g_test.long_serial), m * sizeof(uint32_t), hipHostMallocDefault);
+            if (e != hipSuccess) return hip_fail(e, "long-stream statistics");
+            g_test.long_serial_cap = m;
+        }
+        // stream-ordered after resolve_par_kernel, before the caller can release the workspace
+        e = hipMemcpyAsync(g_test.long_serial, w + L.off_serial, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return hip_fail(e, "long-stream statistics");
+        g_test.long_streams = m;
+        g_test.long_seen = true;
+    }
+    return 0;
 }
 
 int launch_split_long(const Algo& algo, const uint8_t* d_data, uint64_t len, uint64_t* d_cuts, uint64_t cuts_cap,
@@ -4364,8 +4390,23 @@ extern "C" int kcdc_test_set(int32_t key, int64_t value) {
                 return set_error(-22, "help window: 0 (policy), 255 (whole regions), or tiles in [3, 254]");
             g_test.help_window = static_cast<uint32_t>(value);
             return 0;
+        case 10:                                                           // KCDC_TEST_PAR_NODE_CAP
+            if (value < 0 || static_cast<uint64_t>(value) > kParNodeCap)
+                return set_error(-22, "parallel-resolver node cap: 0 (default), or nodes in [1, 2^20]");
+            g_test.par_node_cap = static_cast<uint64_t>(value);
+            return 0;
+        case 11: g_test.long_stat = value != 0; return 0;                  // KCDC_TEST_LONG_STAT
         default: return set_error(-22, "unknown test knob");
     }
+}
+
+extern "C" int64_t kcdc_test_long_stat(int32_t key) {
+    if (key != 1 && key != 2) return set_error(-22, "unknown long-stream statistic");
+    if (!g_test.long_seen) return set_error(-22, "no long-stream launch recorded (KCDC_TEST_LONG_STAT)");
+    if (key == 1) return static_cast<int64_t>(g_test.long_streams);
+    int64_t serial = 0;
+    for (uint32_t j = 0; j < g_test.long_streams; j++) serial += g_test.long_serial[j] != 0;
+    return serial;
 }
 
 extern "C" int64_t kcdc_test_queue_stat(int32_t key) {

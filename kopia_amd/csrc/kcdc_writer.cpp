@@ -1239,7 +1239,11 @@ struct Inside {
         c->inside++;
         ok = !c->closing.load();
     }
-    ~Inside() { c->inside--; }
+    ~Inside() { release(); }
+    void release() {  // leave early: a caller that goes on to wait for the closer must not hold it up
+        if (c) c->inside--;
+        c = nullptr;
+    }
 };
 
 int dev_error(BwDev* b) { return set_error(b->error, b->errmsg); }  // errmsg is set before error
@@ -1641,6 +1645,7 @@ extern "C" void kcdc_bw_free(kcdc_bw* w) {
     const std::shared_ptr<BwCtl> ctl = w->ctl;  // (outlives `in`: w and the batcher may hold the last references)
     Inside in(ctl.get());
     if (!in.ok) {  // the batcher is closing: once it has detached this writer, free what is left
+        in.release();  // kcdc_bw_batcher_free sets `detached` only after `inside` has drained
         while (!ctl->detached.load()) std::this_thread::sleep_for(std::chrono::microseconds(50));
         if (w->arena) {
             Guard g(w->device);

@@ -253,3 +253,59 @@ def test_writer_calls_racing_batcher_free():
             lib.kcdc_bw_free(h)
         flat = [c for g in codes for c in g]
         assert set(flat) <= {0, _lib.KCDC_EINVAL}, set(flat)
+
+
+def test_writer_free_racing_batcher_free():
+    """kcdc_bw_free may race kcdc_bw_batcher_free (include/kcdc.h documents it): a free that finds
+    the batcher closing waits until the batcher has detached its writers, and the batcher detaches
+    them only once no call is inside -- so that free must not count as inside while it waits, or
+    both wait for ever.  Per repetition, on FIXED writers (host logic, no GPU): four threads loop
+    kcdc_bw_write from before the close, four free their writers and one frees the batcher, all
+    released by one event.  The threads are daemons and the closer is joined with a limit, so a
+    deadlock fails this test instead of hanging the suite."""
+    import threading
+    import time
+    from kopia_amd.writer import WriterBatcher
+    lib = _lib.lib()
+    buf = b"z" * 5000
+    for rep in range(100):
+        b = WriterBatcher("FIXED-128K")
+        hs = [lib.kcdc_bw_open(b._h) for _ in range(8)]
+        assert all(hs)
+        hammered, freed = hs[:4], hs[4:]
+        bh, b._h = b._h, None
+        codes, stop, go = [], threading.Event(), threading.Event()
+
+        def hammer(h):
+            got = set()
+            while not stop.is_set():
+                got.add(lib.kcdc_bw_write(h, buf, len(buf)))
+            codes.append(got)
+
+        def free(h, delay):
+            go.wait()
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < delay:
+                pass
+            lib.kcdc_bw_free(h)
+
+        def close():
+            go.wait()
+            lib.kcdc_bw_batcher_free(bh)
+
+        writers = [threading.Thread(target=hammer, args=(h,), daemon=True) for h in hammered]
+        freers = [threading.Thread(target=free, args=(h, 20e-6 * k), daemon=True) for k, h in enumerate(freed)]
+        closer = threading.Thread(target=close, daemon=True)
+        for t in writers + freers + [closer]:
+            t.start()
+        go.set()
+        closer.join(10)
+        hung = closer.is_alive()
+        stop.set()
+        assert not hung, f"repetition {rep}: kcdc_bw_batcher_free still waiting after 10 s"
+        for t in freers + writers:
+            t.join(10)
+            assert not t.is_alive(), f"repetition {rep}: a writer call did not return"
+        assert len(codes) == 4 and set().union(*codes) <= {_lib.KCDC_OK, _lib.KCDC_EINVAL}, codes
+        for h in hammered:
+            lib.kcdc_bw_free(h)
