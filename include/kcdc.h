@@ -435,7 +435,13 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
  * KCDC_TEST_STAT_WAVES (the launch's waves).  Every wave exits holding one ticket and every
  * reserved entry is written, so TICKETS - ENTRIES is WAVES (WAVES - 1 when the last stream's
  * final entry is a tombstone nobody waited for).  Synchronous copy; returns the word, or a
- * negative KCDC_E* code. */
+ * negative KCDC_E* code.
+ * kcdc_test_batch_plan: what a batch launch of `nstreams` streams of splitter `algorithm` on
+ * device 0 would run with, the knobs above as they stand: out[0] the bytes per lane segment (the
+ * buzhash kernel's; a Rabin-Karp lane is twice that), out[1] whether waiting waves help (0/1),
+ * out[2] the help window in tiles (0: whole regions), out[3] the launch's waves.  Host code only,
+ * nothing is launched; the tests' tile model checks itself against it.  0, or a negative KCDC_E*
+ * code (unknown or fixed-size splitter, no streams, no device). */
 #define KCDC_TEST_SPIN_CAP 1
 #define KCDC_TEST_NO_STEAL 2
 #define KCDC_TEST_FORCE_ERROR 3
@@ -460,6 +466,7 @@ int kcdc_test_occupy(uint32_t nwg, uint32_t usec, void* hip_stream);
 #define KCDC_TEST_STAT_ENTRIES 11
 #define KCDC_TEST_STAT_WAVES 12
 int64_t kcdc_test_queue_stat(int32_t key);
+int kcdc_test_batch_plan(const char* algorithm, uint32_t nstreams, uint32_t out[4]);
 /* Test hook: copy bytes [off, off + n) of the last pipelined launch's queue workspace (queue
  * header, stream ring, help slots) to host memory at dst; 0 or a negative error. */
 int kcdc_test_ws_copy(void* dst, uint64_t off, uint64_t n);

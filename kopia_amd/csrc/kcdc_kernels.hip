@@ -4425,6 +4425,25 @@ extern "C" int64_t kcdc_test_queue_stat(int32_t key) {
     return e == hipSuccess ? static_cast<int64_t>(v) : hip_fail(e, "queue statistic");
 }
 
+// Test hook: what batch_plan gives a launch of `nstreams` streams of splitter `name` on device 0
+// with the knobs as they stand -- out = {lane_cap, helpers, help_window, launch waves}.  Host only:
+// the tests' geometry model (tests/batch_model.py) checks its lane cap against this.
+extern "C" int kcdc_test_batch_plan(const char* name, uint32_t nstreams, uint32_t out[4]) {
+    const Algo* algo = name ? find_algo(name) : nullptr;
+    if (!algo || !out) return set_error(-22, "batch plan: unknown splitter or null output");
+    if (algo->kind != kBuzhash && algo->kind != kRabinKarp) return set_error(-22, "batch plan: not a pipelined splitter");
+    if (nstreams == 0) return set_error(-22, "batch plan: no streams");
+    int err = 0;
+    const DeviceTables* t = device_tables(0, &err);
+    if (!t) return err;
+    const BatchPlan p = batch_plan(*algo, nstreams, static_cast<unsigned>(t->cus), g_test);
+    out[0] = p.lane_cap;
+    out[1] = p.helpers ? 1u : 0u;
+    out[2] = p.help_window;
+    out[3] = p.grid * p.wg_waves;
+    return 0;
+}
+
 // Test hook: bytes [off, off + n) of the last pipelined launch's queue workspace (header, ring,
 // help slots) to host memory, for post-mortems of a launch (tools/batch_probe.py).
 extern "C" int kcdc_test_ws_copy(void* dst, uint64_t off, uint64_t n) {

@@ -15,7 +15,12 @@ Here the inputs sit between and on the corners:
       candidate-free streams around the lo >= n tail;
   B3  several long streams in one launch (kcdc_split_files_device), serial and parallel mixed;
   B4  the cuts_cap overflow contract of both resolvers;
-  B5  the parallel resolver's node-table fallback (KCDC_TEST_PAR_NODE_CAP).
+  B5  the parallel resolver's node-table fallback (KCDC_TEST_PAR_NODE_CAP);
+  B6  the scan kernels' own seams (cand_scan_dma_kernel, cand_scan_rk_kernel: the batch kernels'
+      feed, their own segment loop): natural planted windows -- no zero byte, a non-zero hash, so
+      every one of their 64 bytes has to be fetched from the right place, which a zero run cannot
+      show -- swept over a 128 KiB segment boundary, the 2 KiB lane boundaries 0|1 and 31|32 and
+      the middle of a lane, where Rabin-Karp's chain A meets chain B.
 
 Every comparison is bit-exact against the C oracle.  Every test first asserts, from the CPU model
 (tests/long_model.py, pinned to the oracle by tests/test_long_model.py), that its input is in the
@@ -27,6 +32,7 @@ from functools import lru_cache
 import numpy as np
 import pytest
 
+import batch_model as bm
 import long_model as lm
 from kopia_amd import _lib, batch
 from kopia_amd import splitter as ks
@@ -92,23 +98,8 @@ BG_LEN = _chain(LINKS_TRUNC, 0)[2] + 64
 @lru_cache(maxsize=1)
 def background() -> np.ndarray:
     """Counter-PRNG bytes without zero bytes and without one candidate of either hash at the
-    1 MiB average: zeros become 1, then every candidate's byte has bit 0 flipped (3 where that
-    would make a zero) until none is left.  Flipping byte p changes the windows ending at
-    p .. p + 63 only, so after the one full pass per hash the re-checks are local."""
-    d = coracle.gen_stream(SEED, 4242, BG_LEN)
-    d[d == 0] = 1
-    todo = np.unique(np.concatenate([lm.candidates(kind, AVG, d) for kind in KINDS]))
-    for _ in range(8):
-        if todo.size == 0:
-            break
-        d[todo] ^= 1
-        d[todo[d[todo] == 0]] = 3
-        todo = np.unique(np.concatenate([lm.candidates_in(kind, AVG, d, int(p), int(p) + lm.WINDOW)
-                                         for kind in KINDS for p in todo] + [np.zeros(0, dtype=np.int64)]))
-    assert todo.size == 0, "scrub did not converge"
-    assert d.all()
-    d.setflags(write=False)
-    return d
+    1 MiB average (batch_model.scrubbed, the scrub the batch kernels' planted tests share)."""
+    return bm.scrubbed(4242, BG_LEN, AVG)
 
 
 def _plant(n, planted) -> np.ndarray:
@@ -400,3 +391,50 @@ def test_par_node_cap_fallback(gpu, kind):
         for i, (_, want, _) in enumerate(items):
             np.testing.assert_array_equal(cuts[base[i]:base[i] + counts[i]], want, f"cap {node_cap} stream {i}")
         assert (cuts[cap:] == SENTINEL).all()
+
+
+# ------------------------------------------------------------------ B6: the scan kernels' seams
+SWEEP_AVG = 64 << 10  # a custom average: min 32 KiB, max 128 KiB, so streams stay at 5 segments
+SWEEP_N = 5 * SEG
+# anchor -> coordinate (stream position + off0) of the seam
+SWEEP_ANCHORS = {"segment 2|3": 3 * SEG, "lane 0|1": 2 * SEG + lm.LANE, "lane 31|32": 2 * SEG + 32 * lm.LANE,
+                 "mid lane 5": 2 * SEG + 5 * lm.LANE + lm.LANE // 2}
+
+
+@lru_cache(maxsize=None)
+def sweep_streams(kind: str, anchor: str):
+    """[(delta, off0, host bytes, expected cuts)]: one natural candidate at the seam + delta, and
+    before it a second one that makes the chunk rule ask for it (every plant decides a cut)."""
+    out = []
+    mn, mx = SWEEP_AVG // 2, 2 * SWEEP_AVG
+    for i, delta in enumerate(range(-65, 66)):
+        off0 = (7 * i + len(anchor)) % 16
+        p = SWEEP_ANCHORS[anchor] - off0 + delta
+        for items in ([("w", p - 40000), ("w", p)], [("w", p)]):
+            host, planted = bm.plant(kind, SWEEP_AVG, SWEEP_N, items)
+            want = lm.rule(planted, SWEEP_N, mn, mx)
+            if p + 1 in want.tolist():
+                break
+        else:
+            raise AssertionError(f"{anchor} delta {delta}: the plant decides no cut")
+        counts, unlisted = lm.segment_stats(planted, off0, SWEEP_N)
+        assert counts.max() <= 2 and unlisted.size == 0
+        np.testing.assert_array_equal(coracle.split_stream_kind(kind, SWEEP_AVG, host), want)
+        out.append((delta, off0, host, want))
+    assert {o for _, o, _, _ in out} == set(range(16))
+    return out
+
+
+@pytest.mark.parametrize("anchor", list(SWEEP_ANCHORS))
+@pytest.mark.parametrize("kind", KINDS)
+def test_scan_seams(gpu, kind, anchor):
+    """Natural candidates within 65 bytes either side of a segment boundary, two lane boundaries
+    and a lane's middle (where Rabin-Karp's chain A meets chain B; a plain step boundary for buzhash):
+    the scan must list each one, whichever lane, chain and
+    segment its window straddles.  No segment is truncated: the parallel resolver takes them."""
+    name = ks.custom_algorithm(kind, SWEEP_AVG)
+    cases = sweep_streams(kind, anchor)
+    buf, ptrs = _arena(gpu, [(host, off0) for _, off0, host, _ in cases])
+    for (delta, off0, host, want), ptr in zip(cases, ptrs):
+        got = _long_alone(gpu, name, ptr, host.size, serial=False)
+        np.testing.assert_array_equal(got, want, f"{kind} {anchor} delta {delta} off0 {off0}")

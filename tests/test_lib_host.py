@@ -106,6 +106,18 @@ def test_gpu_entry_points_fail_loudly_without_device():
         batch.split_batch_host("DYNAMIC-4M-BUZHASH", [data])
 
 
+def test_batch_plan_hook_refuses_what_has_no_plan():
+    """kcdc_test_batch_plan: unknown names, fixed-size splitters and empty launches are refused
+    before any device is touched."""
+    L = _lib.lib()
+    out = (C.c_uint32 * 4)(7, 7, 7, 7)
+    for name, ns in [(b"NO-SUCH-SPLITTER", 8), (b"FIXED-4M", 8), (b"DYNAMIC-4M-BUZHASH", 0)]:
+        assert L.kcdc_test_batch_plan(name, ns, out) == _lib.KCDC_EINVAL, name
+        assert "batch plan" in _lib.last_error()
+    assert L.kcdc_test_batch_plan(b"DYNAMIC-4M-BUZHASH", 8, None) == _lib.KCDC_EINVAL
+    assert list(out) == [7, 7, 7, 7]
+
+
 def test_fixed_streaming_handle_needs_no_device():
     """FIXED reads no data (splitter_fixed.go:15-26): pure host arithmetic."""
     s = ks.GetFactory("FIXED-128K")()
