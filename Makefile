@@ -5,7 +5,7 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 CSRC := kopia_amd/csrc
 OBJ := build/obj
-SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
+SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 LIB := kopia_amd/libkcdc.so
 
@@ -38,7 +38,7 @@ clean:
 build/libkcdc_dbg.so build/libkcdc_trace.so: $(SRCS) $(CSRC)/kcdc_internal.h include/kcdc.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(if $(findstring dbg,$@),-DKCDC_DEBUG_CHECKS=1,-DKCDC_TRACE=1) -shared -o $@ \
-	  $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip \
+	  $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip \
 	  -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
 instrumented: build/libkcdc_dbg.so build/libkcdc_trace.so
 .PHONY: instrumented
@@ -59,7 +59,7 @@ variants:
 	@for v in $(VARIANTS); do \
 	  n=$${v%%:*}; f=$$(echo $${v#*:} | tr ',' ' '); \
 	  echo "variant $$n: $$f"; \
-	  $(HIPCC) $(HIPFLAGS) $$f -shared -o build/variants/libkcdc_$$n.so $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp || exit 1; \
+	  $(HIPCC) $(HIPFLAGS) $$f -shared -o build/variants/libkcdc_$$n.so $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp || exit 1; \
 	done
 .PHONY: variants
 

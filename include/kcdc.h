@@ -392,6 +392,77 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
                                 const uint64_t* d_out_offsets, uint64_t* d_out_lens, uint32_t* d_header_ids,
                                 void* d_work, uint64_t work_bytes, void* hip_stream);
 
+/* ------------------------------------------------------------- error correction
+ * Kopia's ECC layer for many chunks per call: repo/ecc, REED-SOLOMON-CRC32 (ecc_rs_crc.go).  A
+ * repository created with an ECC overhead wraps its encryptor in encryptorWrapper
+ * (repo/format/format_provider.go:115-125, encryptor_wrapper.go:13-37): every sealed chunk goes
+ * through ReedSolomonCrcECC.Encrypt into a pack and through Decrypt out of it.  Stored layout
+ * (ecc_rs_crc.go:157-165):
+ *   ([CRC32][parity shard])+ ([CRC32][data shard])+   over   BE32(len) || chunk || zero padding
+ * with IEEE CRC-32s of the zero-padded shards, big-endian, and the Reed-Solomon code of
+ * klauspost/reedsolomon (go.mod:32): GF(2^8) mod 0x11d, M = V * (V[0:data])^-1, V[r][c] = r^c.
+ * kcdc_ecc_algorithms / kcdc_ecc_default_algorithm: SupportedAlgorithms, ecc.go:23-35, and the one
+ *   registered name (ecc_rs_crc.go:16, 414-418).
+ * kcdc_ecc_params: newReedSolomonCrcECC (ecc_rs_crc.go:37-89) with computeShards
+ *   (ecc_utils.go:5-20), in the reference's float32 arithmetic.  overhead_percent 1..100;
+ *   max_shard_size 0 picks it by overhead (ecc_rs_crc.go:42-59), else 1..2^24.
+ * kcdc_ecc_encoded_size: the exact stored size of a len-byte chunk (computeSizesFromOriginal,
+ *   ecc_rs_crc.go:91-123, and Encrypt's appends); len >= 2^32 - 4 gives KCDC_EFBIG.
+ * kcdc_ecc_decoded_bound: bytes of output slot a stored chunk of stored_len bytes needs
+ *   (computeSizesFromStored, ecc_rs_crc.go:125-155: its data records' payload less the 4 length
+ *   bytes; at least the chunk's length, at most one shard row more).
+ * kcdc_ecc_matrix: the parity rows of the coding matrix, parity x data bytes, row-major
+ *   (reedsolomon.New(data, parity), ecc_rs_crc.go:76-86); data + parity <= 256.
+ * kcdc_ecc_workspace_size: device scratch for decoding (and repairing) nchunks stored chunks of
+ *   total_stored_bytes in all: 256 bad-shard bits per block, about 5 % of the stored bytes.
+ * kcdc_ecc_encode_chunks_device: Encrypt (ecc_rs_crc.go:166-250) of chunk i = [d_offsets[i],
+ *   +d_lens[i]) of d_data (any alignment) to d_out + d_out_offsets[i] (any alignment, room for
+ *   kcdc_ecc_encoded_size bytes).  d_status[i]: 0, or KCDC_EFBIG (nothing is written).
+ *   Asynchronous on hip_stream.
+ * kcdc_ecc_decode_chunks_device: Decrypt (ecc_rs_crc.go:254-350) up to ReconstructData: every
+ *   stored shard's CRC is checked (the geometry comes from d_stored_lens[i] alone; bytes past the
+ *   stored end read as zeros and data shards that start there are not checked, :297-303), the data
+ *   shards' payload goes to d_out + d_out_offsets[i] (room for kcdc_ecc_decoded_bound bytes; bytes
+ *   past d_out_lens[i] hold padding) and the failed shards of every block are recorded in d_work.
+ *   d_status[i]: 0 with d_out_lens[i] the in-band length; KCDC_ECC_DAMAGED if a checked shard
+ *   failed (d_out_lens[i] = 0, the slot holds unverified bytes: call the repair);
+ *   KCDC_EBADMSG if the in-band length exceeds what the stored bytes hold (slot zeroed);
+ *   KCDC_EINVAL if stored_len < 40, the smallest stored size; KCDC_ENOMEM if d_work is too
+ *   small for the chunk's blocks.  Asynchronous on hip_stream.
+ * kcdc_ecc_repair_chunks_device: ReconstructData (ecc_rs_crc.go:325) for the chunks a decode call
+ *   with the same arguments left KCDC_ECC_DAMAGED.  Waits for hip_stream, reads back the statuses
+ *   and the bad-shard masks, inverts one matrix per erasure pattern on the host, rebuilds the
+ *   missing data shards in the output slots on the device and sets status 0 and d_out_lens[i]; a
+ *   chunk with a block that lost more than its parity shards gets KCDC_EBADMSG and a zeroed slot
+ *   ("Error computing ECC", :326-328).  No-op when no chunk is damaged.  Synchronises hip_stream. */
+#define KCDC_ECC_DAMAGED 1 /* d_status of a decoded chunk with failed shards, before the repair */
+typedef struct kcdc_ecc_info {
+    int32_t data_shards, parity_shards, max_shard_size;
+    int32_t threshold_parity_input, threshold_parity_output, threshold_blocks_input, threshold_blocks_output;
+} kcdc_ecc_info;
+int kcdc_ecc_algorithms(const char** names, int cap);
+const char* kcdc_ecc_default_algorithm(void);
+int kcdc_ecc_params(const char* algorithm, int32_t overhead_percent, int32_t max_shard_size, kcdc_ecc_info* out);
+int64_t kcdc_ecc_encoded_size(const char* algorithm, int32_t overhead_percent, int32_t max_shard_size, uint64_t len);
+int64_t kcdc_ecc_decoded_bound(const char* algorithm, int32_t overhead_percent, int32_t max_shard_size,
+                               uint64_t stored_len);
+int kcdc_ecc_matrix(int32_t data_shards, int32_t parity_shards, uint8_t* out);
+uint64_t kcdc_ecc_workspace_size(uint64_t total_stored_bytes, uint32_t nchunks);
+int kcdc_ecc_encode_chunks_device(const char* algorithm, int32_t overhead_percent, int32_t max_shard_size,
+                                  const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_lens,
+                                  uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets, int32_t* d_status,
+                                  void* hip_stream);
+int kcdc_ecc_decode_chunks_device(const char* algorithm, int32_t overhead_percent, int32_t max_shard_size,
+                                  const uint8_t* d_stored, const uint64_t* d_offsets, const uint64_t* d_stored_lens,
+                                  uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets,
+                                  uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes,
+                                  void* hip_stream);
+int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percent, int32_t max_shard_size,
+                                  const uint8_t* d_stored, const uint64_t* d_offsets, const uint64_t* d_stored_lens,
+                                  uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets,
+                                  uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes,
+                                  void* hip_stream);
+
 /* ------------------------------------------------------------- testing
  * Hooks for the library's own tests (not part of the splitter surface).
  * kcdc_test_set: process-wide knobs read by every later batch launch.

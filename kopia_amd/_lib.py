@@ -28,6 +28,7 @@ KCDC_EINVAL = -22
 KCDC_EOVERFLOW = -75
 KCDC_EFBIG = -27
 KCDC_EBADMSG = -74
+KCDC_ECC_DAMAGED = 1  # status of a decoded chunk with failed shards, before the repair
 
 KIND_FIXED, KIND_BUZHASH, KIND_RABINKARP = 0, 1, 2
 COUNT_FAILED = (1 << 64) - 1  # KCDC_COUNT_FAILED: the batch launch failed on the device
@@ -51,6 +52,12 @@ class KcdcError(RuntimeError):
 class AlgoInfo(C.Structure):
     _fields_ = [("kind", C.c_int32), ("pooled", C.c_int32), ("avg", C.c_uint64), ("min_size", C.c_uint64),
                 ("max_size", C.c_uint64), ("mask", C.c_uint64)]
+
+
+class EccInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("data_shards", "parity_shards", "max_shard_size", "threshold_parity_input",
+                                         "threshold_parity_output", "threshold_blocks_input",
+                                         "threshold_blocks_output")]
 
 
 _P = C.c_void_p
@@ -121,6 +128,19 @@ _SIGS = {
     "kcdc_compress_workspace_size": (C.c_uint64, [C.c_uint64, C.c_uint32]),
     "kcdc_compress_chunks_device": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64,
                                               _P]),
+    "kcdc_ecc_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),
+    "kcdc_ecc_default_algorithm": (C.c_char_p, []),
+    "kcdc_ecc_params": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(EccInfo)]),
+    "kcdc_ecc_encoded_size": (C.c_int64, [C.c_char_p, C.c_int32, C.c_int32, C.c_uint64]),
+    "kcdc_ecc_decoded_bound": (C.c_int64, [C.c_char_p, C.c_int32, C.c_int32, C.c_uint64]),
+    "kcdc_ecc_matrix": (C.c_int, [C.c_int32, C.c_int32, _P]),
+    "kcdc_ecc_workspace_size": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "kcdc_ecc_encode_chunks_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P,
+                                                _P]),
+    "kcdc_ecc_decode_chunks_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P,
+                                                _P, _P, C.c_uint64, _P]),
+    "kcdc_ecc_repair_chunks_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P,
+                                                _P, _P, C.c_uint64, _P]),
 }
 
 

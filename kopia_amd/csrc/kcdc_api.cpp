@@ -1031,3 +1031,56 @@ extern "C" int kcdc_gorand_read(int64_t seed, uint8_t* out, uint64_t n) {
     gorand_read(seed, out, n);
     return KCDC_OK;
 }
+
+// =================================================================== error correction (host side)
+// repo/ecc: the registry (ecc.go:16-46) and the size arithmetic of ReedSolomonCrcECC
+// (ecc_rs_crc.go:37-155).  Host code only; the chunk entry points are in kcdc_ecc.hip.
+extern "C" int kcdc_ecc_algorithms(const char** names, int cap) {
+    if (names && cap > 0) names[0] = "REED-SOLOMON-CRC32";
+    return 1;
+}
+
+extern "C" const char* kcdc_ecc_default_algorithm(void) { return "REED-SOLOMON-CRC32"; }
+
+static int ecc_lookup(const char* alg, int32_t overhead, int32_t max_shard, EccParams* p) {
+    if (!ecc_known(alg)) return set_error(KCDC_ENOENT, std::string("unknown ECC algorithm: ") + (alg ? alg : "(null)"));
+    return ecc_params(overhead, max_shard, p);
+}
+
+extern "C" int kcdc_ecc_params(const char* alg, int32_t overhead_percent, int32_t max_shard_size, kcdc_ecc_info* out) {
+    EccParams p{};
+    if (!out) return set_error(KCDC_EINVAL, "null argument");
+    const int rc = ecc_lookup(alg, overhead_percent, max_shard_size, &p);
+    if (rc) return rc;
+    out->data_shards = static_cast<int32_t>(p.data);
+    out->parity_shards = static_cast<int32_t>(p.parity);
+    out->max_shard_size = static_cast<int32_t>(p.max_shard);
+    out->threshold_parity_input = static_cast<int32_t>(p.thr_parity_in);
+    out->threshold_parity_output = static_cast<int32_t>(p.thr_parity_out);
+    out->threshold_blocks_input = static_cast<int32_t>(p.thr_blocks_in);
+    out->threshold_blocks_output = static_cast<int32_t>(p.thr_blocks_out);
+    return KCDC_OK;
+}
+
+extern "C" int64_t kcdc_ecc_encoded_size(const char* alg, int32_t overhead_percent, int32_t max_shard_size, uint64_t len) {
+    EccParams p{};
+    const int rc = ecc_lookup(alg, overhead_percent, max_shard_size, &p);
+    if (rc) return rc;
+    if (len >= 0xFFFFFFFFull - 3) return set_error(KCDC_EFBIG, "chunk too long for the 4-byte ECC length prefix");
+    return static_cast<int64_t>(ecc_stored_size(ecc_geo_original(p, len), len));
+}
+
+extern "C" int64_t kcdc_ecc_decoded_bound(const char* alg, int32_t overhead_percent, int32_t max_shard_size,
+                                          uint64_t stored_len) {
+    EccParams p{};
+    const int rc = ecc_lookup(alg, overhead_percent, max_shard_size, &p);
+    if (rc) return rc;
+    if (stored_len > (uint64_t(1) << 40)) return set_error(KCDC_EFBIG, "stored chunk too long");
+    const uint64_t pay = ecc_stored_payload(ecc_geo_stored(p, stored_len), stored_len);
+    return pay > kEccLengthSize ? static_cast<int64_t>(pay - kEccLengthSize) : 0;
+}
+
+extern "C" int kcdc_ecc_matrix(int32_t data_shards, int32_t parity_shards, uint8_t* out) {
+    if (data_shards < 1 || parity_shards < 1) return set_error(KCDC_EINVAL, "coding matrix: shard counts must be positive");
+    return ecc_matrix(static_cast<uint32_t>(data_shards), static_cast<uint32_t>(parity_shards), out);
+}

@@ -125,4 +125,80 @@ int launch_hash_chains(const char* name, const uint8_t* key, uint32_t key_len, H
                        const HashChain* fresh, const uint32_t* d_active, uint32_t nactive, uint64_t max_blocks,
                        uint8_t* d_digests, uint32_t digest_stride, void* stream);
 
+// ---- error correction (repo/ecc): parameters and geometry, shared by the host code and kcdc_ecc.hip
+#if defined(__HIPCC__)
+#define KCDC_HD __host__ __device__
+#else
+#define KCDC_HD
+#endif
+constexpr uint32_t kEccLengthSize = 4, kEccCrcSize = 4;              // ecc_rs_crc.go:18-19
+constexpr uint32_t kEccSmallData = 6, kEccSmallParity = 2;           // smallFilesDataShards / ParityShards
+constexpr uint64_t kEccMinStored = 40;                               // (6 + 2) * (4 + 1): the stored size of 0..2 bytes
+constexpr int32_t kEccMaxShardSize = 1 << 24;                        // the largest MaxShardSize this library takes
+struct EccParams {  // newReedSolomonCrcECC, ecc_rs_crc.go:37-89
+    uint32_t data, parity, max_shard;
+    uint64_t thr_parity_in, thr_parity_out, thr_blocks_in, thr_blocks_out;
+};
+struct EccGeo {  // sizesInfo, ecc_rs_crc.go:401-408
+    uint32_t data, parity, shard;
+    uint64_t blocks;
+    bool pad, small;  // StorePadding; the 6+2 code
+    KCDC_HD uint32_t shards() const { return data + parity; }
+    KCDC_HD uint64_t rec() const { return uint64_t(shard) + kEccCrcSize; }
+    KCDC_HD uint64_t parity_bytes() const { return blocks * parity * rec(); }
+};
+KCDC_HD inline uint64_t ecc_ceil(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+// computeSizesFromOriginal (ecc_rs_crc.go:91-123); len < 2^32 - 4
+KCDC_HD inline EccGeo ecc_geo_original(const EccParams& p, uint64_t len) {
+    const uint64_t l = len + kEccLengthSize;
+    EccGeo g{};
+    if (l <= p.thr_parity_in) {
+        g = EccGeo{kEccSmallData, kEccSmallParity, uint32_t(ecc_ceil(l, kEccSmallData)), 1, true, true};
+    } else if (l <= p.thr_blocks_in) {
+        g = EccGeo{p.data, p.parity, uint32_t(ecc_ceil(l, p.data)), 1, true, false};
+    } else {
+        g = EccGeo{p.data, p.parity, p.max_shard, ecc_ceil(l, uint64_t(p.data) * p.max_shard), false, false};
+    }
+    return g;
+}
+// computeSizesFromStored (ecc_rs_crc.go:125-155)
+KCDC_HD inline EccGeo ecc_geo_stored(const EccParams& p, uint64_t stored) {
+    EccGeo g{};
+    if (stored <= p.thr_parity_out || stored <= p.thr_blocks_out) {
+        const bool small = stored <= p.thr_parity_out;
+        g.data = small ? kEccSmallData : p.data;
+        g.parity = small ? kEccSmallParity : p.parity;
+        uint64_t r = ecc_ceil(stored, g.data + g.parity);
+        if (r < 1 + kEccCrcSize) r = 1 + kEccCrcSize;
+        g.shard = uint32_t(r - kEccCrcSize);
+        g.blocks = 1;
+        g.pad = true;
+        g.small = small;
+    } else {
+        g = EccGeo{p.data, p.parity, p.max_shard, 0, false, false};
+        g.blocks = ecc_ceil(stored, uint64_t(g.shards()) * g.rec());
+    }
+    return g;
+}
+// Bytes a len-byte chunk is stored in (computeFinalFileSize, ecc_rs_crc_test.go:171-182).
+KCDC_HD inline uint64_t ecc_stored_size(const EccGeo& g, uint64_t len) {
+    if (g.pad) return uint64_t(g.shards()) * g.rec() * g.blocks;
+    const uint64_t l = len + kEccLengthSize;
+    return g.parity_bytes() + l + ecc_ceil(l, g.shard) * kEccCrcSize;
+}
+// Payload bytes of the data records a stored chunk holds or implies (the logical input, with
+// its 4 length bytes), and with that the room its output slot needs: payload - 4.
+KCDC_HD inline uint64_t ecc_stored_payload(const EccGeo& g, uint64_t stored) {
+    if (g.pad) return uint64_t(g.data) * g.shard;
+    if (stored <= g.parity_bytes()) return 0;
+    const uint64_t dr = stored - g.parity_bytes(), full = dr / g.rec(), rem = dr % g.rec();
+    return full * g.shard + (rem > kEccCrcSize ? rem - kEccCrcSize : 0);
+}
+bool ecc_known(const char* name);                                        // "REED-SOLOMON-CRC32"
+int ecc_params(int32_t overhead_percent, int32_t max_shard_size, EccParams* out);  // 0 or -22 (sets the error)
+// Parity rows (parity x data, row-major) of the klauspost/reedsolomon coding matrix.
+int ecc_matrix(uint32_t data, uint32_t parity, uint8_t* out);
+uint8_t gf_mul(uint8_t a, uint8_t b);
+uint8_t gf_inv(uint8_t a);
+
 }  // namespace kcdc
