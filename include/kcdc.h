@@ -491,6 +491,12 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
  *                         stream whose nodes do not fit resolves serially, with the same cuts.
  *   KCDC_TEST_LONG_STAT   1: every long-stream launch records which resolver took each of its
  *                         streams, for kcdc_test_long_stat
+ *   KCDC_TEST_DEFLATE_MAXB the deflate family's launches: the longest literal/length and distance
+ *                         code of a dynamic block, in [9, 15]; 0: the default (15, RFC 1951's limit).
+ *                         A lower limit gives a valid stream and makes the length limiter run on
+ *                         ordinary skewed data.
+ *   KCDC_TEST_DEFLATE_CL_MAXB the same for the dynamic header's code-length code, in [5, 7]; 0: the
+ *                         default (7)
  * kcdc_test_long_stat: after the last long-stream launch made with KCDC_TEST_LONG_STAT on has
  * finished (synchronise first): KCDC_TEST_LONG_STREAMS, the streams of that launch, or
  * KCDC_TEST_LONG_SERIAL, how many of them the serial resolver took (truncated segments, or no
@@ -524,6 +530,8 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
 #define KCDC_TEST_HELP_WINDOW 9
 #define KCDC_TEST_PAR_NODE_CAP 10
 #define KCDC_TEST_LONG_STAT 11
+#define KCDC_TEST_DEFLATE_MAXB 12
+#define KCDC_TEST_DEFLATE_CL_MAXB 13
 int kcdc_test_set(int32_t key, int64_t value);
 #define KCDC_TEST_LONG_STREAMS 1
 #define KCDC_TEST_LONG_SERIAL 2

@@ -30,7 +30,8 @@
 //   zstd     one Compressed_Block per segment: literals Huffman-coded with one code per span
 //            (the first saving segment carries the tree, later ones are Treeless) or raw, the
 //            sequences through the predefined FSE tables, written backwards (zstd_seqs).
-// A segment that would not beat a stored copy is stored.  Segments join by a byte prefix sum
+// A segment that would not beat a stored copy is stored (deflate: unless the span's stored
+// segments are skewed enough for its dynamic code, see deflate_plan).  Segments join by a byte prefix sum
 // (span_pos), deflate_copy_kernel places them, deflate_frame_kernel writes the header ID, the
 // format's frame (gzip member with CRC-32 and ISIZE, zstd frame header, final empty block) and
 // the kept-or-dropped ID (NoCompression when the output is not smaller).
@@ -95,6 +96,8 @@ struct CompArgs {
     uint32_t* span_crc; // [max_spans]: S2, each span's raw CRC-32C
     uint32_t x2n[32];   // x^(2^k) mod P, CRC-32's reflected polynomial (zlib x2n_table)
     uint32_t x2nc[32];  // the same for CRC-32C (Castagnoli, S2 framing)
+    uint32_t maxb_ll;   // deflate: longest literal/length and distance code, 15 (KCDC_TEST_DEFLATE_MAXB: 9..15)
+    uint32_t maxb_cl;   // deflate: longest code-length code, 7 (KCDC_TEST_DEFLATE_CL_MAXB: 5..7)
 };
 
 __global__ __launch_bounds__(256) void span_count_kernel(CompArgs a) {
@@ -599,7 +602,7 @@ struct OrBits {
 // The dynamic block header (RFC 1951 §3.2.7) for the code lengths len[0..316): HLIT, HDIST,
 // HCLEN, the code-length code's lengths in the permuted order, then the literal/length and
 // distance lengths (one sequence) run-length coded with 16 (the previous length 3-6 times), 17
-// (3-10 zeros) and 18 (11-138 zeros) through that code (lengths <= 7, at least two used symbols:
+// (3-10 zeros) and 18 (11-138 zeros) through that code (lengths <= clmax <= 7, at least two used symbols:
 // inflaters reject an incomplete code-length code).  Bits to hdr[] (LDS words); returns their
 // count.  Wave-parallel: the runs start where a length differs from the one before (a ballot per
 // 64 positions), each run's lane emits its symbols at its offset (a prefix over the runs in order),
@@ -608,7 +611,7 @@ struct OrBits {
 // huff_lengths' sa/ss/num.  Wave-collective.
 __device__ uint32_t dyn_header(const uint8_t* len, uint32_t* hdr, uint16_t* cl, uint32_t* clcnt, uint8_t* cllen,
                                uint32_t* clcode, uint32_t* sa, uint16_t* ss, uint32_t* num, uint32_t* misc,
-                               uint32_t lane) {
+                               uint32_t clmax, uint32_t lane) {
     uint32_t hlit = 257u, hdist = 1u;  // the last used literal/length and distance codes
     for (uint32_t k = 0; k < kNLit; k += 64u) {
         const uint64_t m = __ballot(k + lane < kNLit && len[k + lane] != 0u);
@@ -698,7 +701,7 @@ __device__ uint32_t dyn_header(const uint8_t* len, uint32_t* hdr, uint16_t* cl, 
         }
     }
     wave_sync();
-    huff_lengths(clcnt, 19u, 7u, cllen, sa, ss, num, lane);
+    huff_lengths(clcnt, 19u, clmax, cllen, sa, ss, num, lane);
     canon_codes(cllen, 19u, clcode, lane);
     wave_sync();
     uint32_t hclen = 19u;
@@ -810,7 +813,33 @@ __device__ __forceinline__ void deflate_plan(const CompArgs& a, uint32_t b, uint
     uint32_t* num = S + 1184;                              // 33
     uint32_t* misc = S + 1220;                             // 8
     const uint32_t seg_len = x0 < span_len ? min(kSeg, span_len - x0) : 0u, xe = x0 + seg_len;
-    const bool coded = seg_len && !(word & kStored);
+    bool coded = seg_len && !(word & kStored);
+    // Segments the parse marked stored (its test is the FIXED code: a segment with no match never
+    // passes it) are coded after all, as literals only, when their bytes are skewed enough for a
+    // dynamic code: with c[v] their byte counts and N their bytes, sum c[v] * (floor(log2(N / c[v]))
+    // + 1) bounds their entropy from above; below 7 bits a byte (and 1024 bits for a header) they
+    // join the span's code.  Uniform bytes (random data) measure 8 to 10 bits and stay stored.
+    const bool stored0 = seg_len && (word & kStored);
+    if (a.effort >= 1u && __ballot(stored0)) {
+        uint32_t* hist2 = S + 1760;  // 256 words, free until the plan's scratch below is written
+        for (uint32_t k = lane; k < 256u; k += 64u) hist2[k] = 0u;
+        __syncthreads();
+        if (stored0)
+            for (uint32_t x = x0; x < xe; x++) atomicAdd(&hist2[st_byte(L, d, x)], 1u);
+        __syncthreads();
+        uint32_t n2 = stored0 ? seg_len : 0u, est = 0u;
+        for (uint32_t o = 32; o > 0; o >>= 1) n2 += static_cast<uint32_t>(__shfl_xor(n2, static_cast<int>(o), 64));
+        for (uint32_t k = lane; k < 256u; k += 64u) {
+            const uint32_t c = hist2[k];
+            if (c) est += c * (32u - static_cast<uint32_t>(__builtin_clz(n2 / c)));
+        }
+        for (uint32_t o = 32; o > 0; o >>= 1) est += static_cast<uint32_t>(__shfl_xor(est, static_cast<int>(o), 64));
+        __syncthreads();
+        if (est + 1024u <= 7u * n2 && stored0) {
+            coded = true;
+            nm = 0u;  // the parse's tokens of a segment it gave up on are not complete
+        }
+    }
     const uint32_t* tok = reinterpret_cast<const uint32_t*>(a.slots + (static_cast<uint64_t>(b) * 64u + lane) * kSlot);
     const uint64_t cm = __ballot(coded);
     const bool dynamic = cm != 0ull && a.effort >= 1u;
@@ -835,10 +864,10 @@ __device__ __forceinline__ void deflate_plan(const CompArgs& a, uint32_t b, uint
             }
         }
         __syncthreads();
-        huff_lengths(hist, kNLit, 15u, lens, S + 1232, ss, num, lane);  // (512 words: free from 1228)
-        huff_lengths(hist + kNLit, kNDist, 15u, lens + kNLit, sa, ss, num, lane);
+        huff_lengths(hist, kNLit, a.maxb_ll, lens, S + 1232, ss, num, lane);  // (512 words: free from 1228)
+        huff_lengths(hist + kNLit, kNDist, a.maxb_ll, lens + kNLit, sa, ss, num, lane);
         KCDC_DSTAMP(3);
-        hb = dyn_header(lens, hdr, cl, clcnt, cllen, clcode, sa, ss, num, misc, lane);
+        hb = dyn_header(lens, hdr, cl, clcnt, cllen, clcode, sa, ss, num, misc, a.maxb_cl, lane);
     }
     KCDC_DSTAMP(4);
     uint32_t bd = 0, bf = 0;  // the segment's bits under the dynamic / the fixed code
@@ -2808,6 +2837,9 @@ const CompAlgo* find_comp(const char* name) {
 
 uint64_t align256c(uint64_t x) { return (x + 255u) & ~uint64_t(255); }
 
+// kcdc_test_set(KCDC_TEST_DEFLATE_MAXB / _CL_MAXB): lower code-length limits (0: RFC 1951's 15 and 7)
+uint32_t g_test_maxb_ll = 0, g_test_maxb_cl = 0;
+
 struct CompWs {
     uint64_t spans, crc, span_crc, seglen, span_bytes, span_pos, slots, desc, total;
 };
@@ -2830,6 +2862,16 @@ CompWs comp_ws(uint32_t n, uint64_t max_spans) {
 }  // namespace kcdc
 
 using namespace kcdc;
+
+namespace kcdc {
+int test_set_deflate_limit(bool cl, int64_t value) {
+    if (value != 0 && (value < (cl ? 5 : 9) || value > (cl ? 7 : 15)))
+        return set_error(-22, cl ? "deflate code-length code limit: 0 (default 7), or bits in [5, 7]"
+                                 : "deflate code limit: 0 (default 15), or bits in [9, 15]");
+    (cl ? g_test_maxb_cl : g_test_maxb_ll) = static_cast<uint32_t>(value);
+    return 0;
+}
+}  // namespace kcdc
 
 extern "C" int kcdc_compression_algorithms(const char** names, int cap) {
     const int n = static_cast<int>(sizeof(kCompAlgos) / sizeof(kCompAlgos[0]));
@@ -2889,6 +2931,8 @@ extern "C" int kcdc_compress_chunks_device(const char* name, const uint8_t* d_da
     a.effort = al->effort;
     a.gzip = al->gzip;
     a.fmt = al->fmt;
+    a.maxb_ll = g_test_maxb_ll ? g_test_maxb_ll : 15u;
+    a.maxb_cl = g_test_maxb_cl ? g_test_maxb_cl : 7u;
     a.crc = reinterpret_cast<uint32_t*>(w + l.crc);
     a.span_crc = reinterpret_cast<uint32_t*>(w + l.span_crc);
     {

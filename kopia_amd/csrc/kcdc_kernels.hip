@@ -4396,6 +4396,8 @@ extern "C" int kcdc_test_set(int32_t key, int64_t value) {
             g_test.par_node_cap = static_cast<uint64_t>(value);
             return 0;
         case 11: g_test.long_stat = value != 0; return 0;                  // KCDC_TEST_LONG_STAT
+        case 12: return test_set_deflate_limit(false, value);              // KCDC_TEST_DEFLATE_MAXB
+        case 13: return test_set_deflate_limit(true, value);               // KCDC_TEST_DEFLATE_CL_MAXB
         default: return set_error(-22, "unknown test knob");
     }
 }

@@ -88,17 +88,24 @@ def test_reference_properties(name, gpu):
                 deflate.decompress(other, blob)
 
 
-@pytest.mark.parametrize("name", ["deflate-default", "gzip", "pgzip-best-speed", "s2-default", "s2-better",
-                                  "zstd", "zstd-best-compression"])
-def test_ragged_misaligned_chunks(name, gpu):
-    """Edge lengths around the 512-byte segments and 32 KiB spans at random offsets; for the gzip
-    family this exercises the device CRC-32 (end-aligned spans, partial first span)."""
+def ragged_corpus():
+    """(host bytes, offsets, lengths) of test_ragged_misaligned_chunks; tools/deflate_census.py
+    reports which branches of the deflate plan these chunks reach."""
     host = _mixed(24 << 20, 11)
     rng = np.random.default_rng(12)
     edge = [0, 1, 2, 3, 4, 5, 7, 8, 255, 511, 512, 513, 1023, 1024, 1025, 4096, 32767, 32768, 32769,
             65535, 65536, 65537, 100000, (1 << 20) + 3]
     lens = edge + [int(x) for x in rng.integers(0, 300000, 200)]
     offs = [int(rng.integers(0, host.size - L)) for L in lens]
+    return host, offs, lens
+
+
+@pytest.mark.parametrize("name", ["deflate-default", "gzip", "pgzip-best-speed", "s2-default", "s2-better",
+                                  "zstd", "zstd-best-compression"])
+def test_ragged_misaligned_chunks(name, gpu):
+    """Edge lengths around the 512-byte segments and 32 KiB spans at random offsets; for the gzip
+    family this exercises the device CRC-32 (end-aligned spans, partial first span)."""
+    host, offs, lens = ragged_corpus()
     out, oo, ol, ids = _compress(name, host, offs, lens, gpu)
     _check(name, host, offs, lens, out, oo, ol, ids)
     assert (ids != 0).sum() > len(lens) // 2  # mixed data mostly compresses
