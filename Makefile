@@ -11,11 +11,14 @@ LIB := kopia_amd/libkcdc.so
 
 all: $(LIB) oracle build/writer_bench
 
-$(OBJ)/%.hip.o: $(CSRC)/%.hip $(CSRC)/kcdc_internal.h include/kcdc.h
+# every object depends on every header of the sources' directory: a header edit rebuilds
+HDRS := $(wildcard $(CSRC)/*.h) include/kcdc.h
+
+$(OBJ)/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/kcdc_internal.h include/kcdc.h
+$(OBJ)/%.cpp.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -25,7 +28,7 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(CSRC)/kcdc_kernels.hip
+asm: $(CSRC)/kcdc_kernels.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o build/asm/kcdc_kernels.s -Rpass-analysis=kernel-resource-usage 2> build/asm/resource.txt
 
@@ -35,7 +38,7 @@ clean:
 
 # Instrumented builds for tools/debug_pipe.py (queue invariants, KCDC_DEBUG_CHECKS) and
 # tools/trace_pipe.py (per-wave s_memrealtime trace, KCDC_TRACE); not used by the product.
-build/libkcdc_dbg.so build/libkcdc_trace.so: $(SRCS) $(CSRC)/kcdc_internal.h include/kcdc.h
+build/libkcdc_dbg.so build/libkcdc_trace.so: $(SRCS) $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(if $(findstring dbg,$@),-DKCDC_DEBUG_CHECKS=1,-DKCDC_TRACE=1) -shared -o $@ \
 	  $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip \

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/kcdc.h"
+#include "kcdc_hip.h"
 #include "kcdc_internal.h"
 
 namespace kcdc {
@@ -24,24 +25,11 @@ using namespace kcdc;
 
 namespace {
 
-int hip_err(hipError_t e, const char* what) { return set_error(KCDC_EIO, std::string(what) + ": " + hipGetErrorString(e)); }
-
 #define HIP_TRY(expr, what)                          \
     do {                                             \
         hipError_t e_ = (expr);                      \
-        if (e_ != hipSuccess) return hip_err(e_, what); \
+        if (e_ != hipSuccess) return hip_error(e_, what); \
     } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 bool is_gfx950(int dev) {
     hipDeviceProp_t p;
@@ -137,18 +125,14 @@ struct kcdc_splitter {
     hipStream_t stream = nullptr;
     int64_t count = 0;              // rs.count (rolling) / s.cur (fixed)
     uint8_t hist[kWindow] = {0};    // last 64 stream bytes (zeros before the start)
-    uint8_t* h_stage = nullptr;     // pinned: hist || slice
-    uint8_t* d_stage = nullptr;
-    uint8_t* d_scratch = nullptr;   // zero-copy: device memory the fallback scan copies the staging into
+    uint8_t* h_stage = nullptr;     // pinned, mapped: hist || slice (the scans read it in place)
+    uint8_t* d_stage = nullptr;     // its device mapping
+    uint8_t* d_scratch = nullptr;   // device memory a launched scan copies the staging into
     size_t stage_cap = 0;
-    int64_t* d_out = nullptr;
-    int64_t* h_out = nullptr;
+    int64_t* h_out = nullptr;       // pinned, mapped: a launched scan's one-word answer
+    int64_t* d_out = nullptr;       // its device mapping
     kcdc_group* group = nullptr;  // set: GPU scans are batched with the group's other handles
 };
-
-#ifndef KCDC_HANDLE_ZC
-#define KCDC_HANDLE_ZC 1  // private handles: the scan reads the pinned staging in place (mapped)
-#endif
 
 namespace {
 
@@ -170,26 +154,19 @@ void push_hist(kcdc_splitter* s, const uint8_t* b, size_t n) {
 void destroy(kcdc_splitter* s) {
     if (!s) return;
     DeviceGuard g(s->device);
-    if (s->d_stage && !KCDC_HANDLE_ZC) (void)hipFree(s->d_stage);  // zero-copy: a mapping of h_stage
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
+    if (s->h_stage) (void)hipHostFree(s->h_stage);  // (d_stage and d_out are mappings)
     if (s->d_scratch) (void)hipFree(s->d_scratch);
-    if (s->d_out && !KCDC_HANDLE_ZC) (void)hipFree(s->d_out);
     if (s->h_out) (void)hipHostFree(s->h_out);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
 
-// The one-word answer of a private scan (zero-copy: written by the kernel into mapped host memory).
+// The one-word answer of a private scan, written by the kernel into mapped host memory.
 hipError_t alloc_out(kcdc_splitter* s) {
-    if (KCDC_HANDLE_ZC) {
-        hipError_t e = hipHostMalloc(&s->h_out, sizeof(int64_t), hipHostMallocMapped);
-        void* pd = nullptr;
-        if (e == hipSuccess) e = hipHostGetDevicePointer(&pd, s->h_out, 0);
-        s->d_out = static_cast<int64_t*>(pd);
-        return e;
-    }
-    hipError_t e = hipMalloc(&s->d_out, sizeof(int64_t));
-    if (e == hipSuccess) e = hipHostMalloc(&s->h_out, sizeof(int64_t), hipHostMallocDefault);
+    hipError_t e = hipHostMalloc(&s->h_out, sizeof(int64_t), hipHostMallocMapped);
+    void* pd = nullptr;
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&pd, s->h_out, 0);
+    s->d_out = static_cast<int64_t*>(pd);
     return e;
 }
 
@@ -198,25 +175,19 @@ int ensure_stage(kcdc_splitter* s, size_t need) {
     size_t cap = std::max<size_t>(need, 1 << 20);
     cap = std::min<size_t>(std::max(cap, s->stage_cap * 2), s->algo->max_size() + 2 * kWindow);
     cap = std::max(cap, need);
-    if (s->d_stage && !KCDC_HANDLE_ZC) (void)hipFree(s->d_stage);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->d_scratch) (void)hipFree(s->d_scratch);
     s->d_stage = nullptr;
     s->h_stage = nullptr;
     s->d_scratch = nullptr;
     s->stage_cap = 0;
-    if (KCDC_HANDLE_ZC) {
-        // fine-grained: the resident scan server reads it between requests without a kernel
-        // boundary, so no stale cached copy may survive
-        HIP_TRY(hipHostMalloc(&s->h_stage, cap, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stage");
-        void* pd = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&pd, s->h_stage, 0), "stage mapping");
-        s->d_stage = static_cast<uint8_t*>(pd);
-        HIP_TRY(hipMalloc(&s->d_scratch, cap), "hipMalloc scan scratch");
-    } else {
-        HIP_TRY(hipMalloc(&s->d_stage, cap), "hipMalloc stage");
-        HIP_TRY(hipHostMalloc(&s->h_stage, cap, hipHostMallocDefault), "hipHostMalloc stage");
-    }
+    // fine-grained: the resident scan server reads it between requests without a kernel
+    // boundary, so no stale cached copy may survive
+    HIP_TRY(hipHostMalloc(&s->h_stage, cap, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc stage");
+    void* pd = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&pd, s->h_stage, 0), "stage mapping");
+    s->d_stage = static_cast<uint8_t*>(pd);
+    HIP_TRY(hipMalloc(&s->d_scratch, cap), "hipMalloc scan scratch");
     s->stage_cap = cap;
     return KCDC_OK;
 }
@@ -237,27 +208,21 @@ int64_t gpu_first_candidate(kcdc_splitter* s, const uint8_t* b, size_t n) {
     if (rc) return rc;
     std::memcpy(s->h_stage, s->hist, kWindow);
     std::memcpy(s->h_stage + kWindow, b, n);
-    if (KCDC_HANDLE_ZC) {
-        // The resident scan server (no launch, tables already in LDS) when this is the only open
-        // private handle: the server is one workgroup, so concurrent writers would queue on it,
-        // while launches of their own run side by side (16 writers: 12.5 GB/s launching, 7.1
-        // through the server).
-        if (g_open_private.load(std::memory_order_acquire) == 1) {
-            int64_t f = -1;
-            const int rs = server_scan_first(*s->algo, s->d_stage, total, kWindow, static_cast<int64_t>(total) - 1,
-                                             s->device, &f);
-            if (rs < 0) return rs;
-            if (rs == 0) return f < 0 ? -1 : f - kWindow;
-        }
-        // other scans in flight, or the server is busy or unavailable: a launch of our own
+    // The resident scan server (no launch, tables already in LDS) when this is the only open
+    // private handle: the server is one workgroup, so concurrent writers would queue on it,
+    // while launches of their own run side by side (16 writers: 12.5 GB/s launching, 7.1
+    // through the server).
+    if (g_open_private.load(std::memory_order_acquire) == 1) {
+        int64_t f = -1;
+        const int rs = server_scan_first(*s->algo, s->d_stage, total, kWindow, static_cast<int64_t>(total) - 1,
+                                         s->device, &f);
+        if (rs < 0) return rs;
+        if (rs == 0) return f < 0 ? -1 : f - kWindow;
     }
-    if (!KCDC_HANDLE_ZC)
-        HIP_TRY(hipMemcpyAsync(s->d_stage, s->h_stage, total, hipMemcpyHostToDevice, s->stream), "H2D slice");
+    // other scans in flight, or the server is busy or unavailable: a launch of our own
     rc = launch_scan_first(*s->algo, s->d_stage, total, kWindow, static_cast<int64_t>(total) - 1, s->d_out, s->device,
                            s->stream, s->d_scratch);
     if (rc) return rc;
-    if (!KCDC_HANDLE_ZC)
-        HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream), "D2H result");
     HIP_TRY(hipStreamSynchronize(s->stream), "scan sync");
     const int64_t f = s->h_out[0];
     return f < 0 ? -1 : f - kWindow;
@@ -384,12 +349,10 @@ extern "C" void kcdc_splitter_close(kcdc_splitter* s) {
 // Many object writers run at once (snapshot/upload/upload.go:769-782), each calling
 // NextSplitPoint on its own splitter with a 64 KiB slice.  Alone, each call is one GPU
 // round trip.  A group gathers the calls of all its handles that arrive together into one
-// launch (one wave per call): writers copy "history ‖ slice" into the open pinned staging
-// buffer in parallel, the group thread seals it, ships it (H2D, kernel, D2H) while the
-// writers fill the other buffer, and hands every writer its answer.
-#ifndef KCDC_GROUP_ZC
-#define KCDC_GROUP_ZC 1  // the scan reads the pinned staging in place (mapped), answers land in host memory
-#endif
+// launch (one workgroup per call): writers copy "history ‖ slice" into the open pinned staging
+// buffer in parallel, the group thread seals it and launches the scan, which reads the staging
+// in place (mapped) and writes the answers into host memory, while the writers fill the other
+// buffer; then it hands every writer its answer.
 struct kcdc_group {
     const Algo* algo = nullptr;
     int device = 0;
@@ -398,8 +361,8 @@ struct kcdc_group {
     std::chrono::microseconds wait{0};
     struct Buf {
         uint8_t* h = nullptr;  // pinned staging
-        uint8_t* d = nullptr;  // its device copy, or (KCDC_GROUP_ZC) its device mapping
-        uint8_t* scratch = nullptr;  // (KCDC_GROUP_ZC) device scratch the scan copies the staging into
+        uint8_t* d = nullptr;  // its device mapping (as d_req, d_out)
+        uint8_t* scratch = nullptr;  // device scratch the scan copies the staging into
         ScanReq* h_req = nullptr;
         ScanReq* d_req = nullptr;
         int64_t* h_out = nullptr;
@@ -431,11 +394,6 @@ void group_release(kcdc_group* g) {
         if (b.h_req) (void)hipHostFree(b.h_req);
         if (b.h_out) (void)hipHostFree(b.h_out);
         if (b.scratch) (void)hipFree(b.scratch);
-        if (!KCDC_GROUP_ZC) {  // device copies (zero-copy: mappings of the host buffers)
-            if (b.d) (void)hipFree(b.d);
-            if (b.d_req) (void)hipFree(b.d_req);
-            if (b.d_out) (void)hipFree(b.d_out);
-        }
     }
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -458,24 +416,10 @@ void group_loop(kcdc_group* g) {
         g->buf[g->open].seq = g->seq_next++;
         g->cv_work.wait(lk, [&] { return B.writing == 0; });
         const uint32_t n = B.n;
-        const size_t used = B.used;
         lk.unlock();
-        int rc = KCDC_OK;
-        hipError_t e = hipSuccess;
-        if (KCDC_GROUP_ZC) {  // the kernel reads the staging and writes the answers over PCIe
-            rc = launch_scan_first_batch(*g->algo, B.d, B.d_req, n, B.d_out, g->device, g->stream, B.scratch);
-        } else {
-            e = hipMemcpyAsync(B.d, B.h, used, hipMemcpyHostToDevice, g->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(B.d_req, B.h_req, n * sizeof(ScanReq), hipMemcpyHostToDevice, g->stream);
-            if (e == hipSuccess) {
-                rc = launch_scan_first_batch(*g->algo, B.d, B.d_req, n, B.d_out, g->device, g->stream);
-                if (rc == KCDC_OK)
-                    e = hipMemcpyAsync(B.h_out, B.d_out, n * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream);
-            }
-        }
-        if (e == hipSuccess && rc == KCDC_OK) e = hipStreamSynchronize(g->stream);
-        if (e != hipSuccess && rc == KCDC_OK) rc = KCDC_EIO;
+        // the kernel reads the staging and writes the answers over PCIe
+        int rc = launch_scan_first_batch(*g->algo, B.d, B.d_req, n, B.d_out, g->device, g->stream, B.scratch);
+        if (rc == KCDC_OK && hipStreamSynchronize(g->stream) != hipSuccess) rc = KCDC_EIO;
         lk.lock();
         for (uint32_t k = 0; k < n; k++) *B.result[k] = rc == KCDC_OK ? B.h_out[k] : rc;
         B.n = 0;
@@ -562,12 +506,11 @@ extern "C" kcdc_group* kcdc_group_new(const char* name, int device, uint32_t max
     g->max_batch = std::max<uint32_t>(1, std::min<uint32_t>(max_batch ? max_batch : 256, 4096));
     g->wait = std::chrono::microseconds(max_wait_us);
     bool ok = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess;
-    const unsigned hflags = KCDC_GROUP_ZC ? hipHostMallocMapped : hipHostMallocDefault;
     for (auto& b : g->buf) {
-        ok = ok && hipHostMalloc(&b.h, kcdc_group::kCap, hflags) == hipSuccess &&
-             hipHostMalloc(&b.h_req, g->max_batch * sizeof(ScanReq), hflags) == hipSuccess &&
-             hipHostMalloc(&b.h_out, g->max_batch * sizeof(int64_t), hflags) == hipSuccess;
-        if (ok && KCDC_GROUP_ZC) {
+        ok = ok && hipHostMalloc(&b.h, kcdc_group::kCap, hipHostMallocMapped) == hipSuccess &&
+             hipHostMalloc(&b.h_req, g->max_batch * sizeof(ScanReq), hipHostMallocMapped) == hipSuccess &&
+             hipHostMalloc(&b.h_out, g->max_batch * sizeof(int64_t), hipHostMallocMapped) == hipSuccess;
+        if (ok) {
             void *pd = nullptr, *pr = nullptr, *po = nullptr;
             ok = hipHostGetDevicePointer(&pd, b.h, 0) == hipSuccess &&
                  hipHostGetDevicePointer(&pr, b.h_req, 0) == hipSuccess &&
@@ -576,10 +519,6 @@ extern "C" kcdc_group* kcdc_group_new(const char* name, int device, uint32_t max
             b.d_req = static_cast<ScanReq*>(pr);
             b.d_out = static_cast<int64_t*>(po);
             ok = ok && hipMalloc(&b.scratch, kcdc_group::kCap) == hipSuccess;
-        } else if (ok) {
-            ok = hipMalloc(&b.d, kcdc_group::kCap) == hipSuccess &&
-                 hipMalloc(&b.d_req, g->max_batch * sizeof(ScanReq)) == hipSuccess &&
-                 hipMalloc(&b.d_out, g->max_batch * sizeof(int64_t)) == hipSuccess;
         }
         if (ok) b.result.resize(g->max_batch);
     }

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/kcdc.h"
+#include "kcdc_hip.h"
 #include "kcdc_internal.h"
 
 namespace kcdc {
@@ -473,8 +474,6 @@ using eccdev::DecArgs;
 using eccdev::EncArgs;
 
 // ------------------------------------------------------------------ host side
-int hip_fail(hipError_t e, const char* what) { return set_error(-5, std::string(what) + ": " + hipGetErrorString(e)); }
-
 // Rows of nin coefficients, each padded with zeros to coef_stride(nin) bytes (rs_rows).
 std::vector<uint8_t> pad_rows(const std::vector<uint8_t>& m, uint32_t rows, uint32_t nin) {
     const uint32_t st = eccdev::coef_stride(nin);
@@ -504,7 +503,7 @@ const uint8_t* device_matrix(const EccParams& p, int* err) {
     if (e == hipSuccess) e = hipMemcpy(d, m.data(), m.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         if (d) (void)hipFree(d);
-        return *err = hip_fail(e, "ECC coding matrix upload"), nullptr;
+        return *err = hip_error(e, "ECC coding matrix upload"), nullptr;
     }
     cache[key] = d;
     return d;
@@ -615,7 +614,7 @@ int upload(const std::vector<T>& v, T** d) {
     if (v.empty()) return 0;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(d), v.size() * sizeof(T));
     if (e == hipSuccess) e = hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e == hipSuccess ? 0 : hip_fail(e, "ECC repair tables upload");
+    return e == hipSuccess ? 0 : hip_error(e, "ECC repair tables upload");
 }
 
 }  // namespace
@@ -644,7 +643,7 @@ extern "C" int kcdc_ecc_encode_chunks_device(const char* alg, int32_t overhead_p
     hipLaunchKernelGGL(eccdev::ecc_parity_kernel, grid, dim3(eccdev::kThreads), 0, st, a);
     hipLaunchKernelGGL(eccdev::ecc_records_kernel<false>, grid, dim3(eccdev::kThreads), 0, st, a, DecArgs{});
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "ECC encode kernel launch");
+    return e == hipSuccess ? 0 : hip_error(e, "ECC encode kernel launch");
 }
 
 extern "C" int kcdc_ecc_decode_chunks_device(const char* alg, int32_t overhead_percent, int32_t max_shard_size,
@@ -658,13 +657,13 @@ extern "C" int kcdc_ecc_decode_chunks_device(const char* alg, int32_t overhead_p
     if (rc || nchunks == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = a.mask_blocks ? hipMemsetAsync(a.masks, 0, a.mask_blocks * 32u, st) : hipSuccess;
-    if (e != hipSuccess) return hip_fail(e, "ECC mask clear");
+    if (e != hipSuccess) return hip_error(e, "ECC mask clear");
     const dim3 grid(nchunks, eccdev::kGridY);
     hipLaunchKernelGGL(eccdev::ecc_decode_init_kernel, dim3(1), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(eccdev::ecc_records_kernel<true>, grid, dim3(eccdev::kThreads), 0, st, EncArgs{}, a);
     hipLaunchKernelGGL(eccdev::ecc_decode_finish_kernel, dim3(nchunks), dim3(eccdev::kThreads), 0, st, a);
     e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "ECC decode kernel launch");
+    return e == hipSuccess ? 0 : hip_error(e, "ECC decode kernel launch");
 }
 
 extern "C" int kcdc_ecc_repair_chunks_device(const char* alg, int32_t overhead_percent, int32_t max_shard_size,
@@ -678,10 +677,10 @@ extern "C" int kcdc_ecc_repair_chunks_device(const char* alg, int32_t overhead_p
     if (rc || nchunks == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "ECC repair: stream sync");
+    if (e != hipSuccess) return hip_error(e, "ECC repair: stream sync");
     std::vector<int32_t> status(nchunks);
     if ((e = hipMemcpy(status.data(), d_status, size_t(nchunks) * 4u, hipMemcpyDeviceToHost)) != hipSuccess)
-        return hip_fail(e, "ECC repair: status readback");
+        return hip_error(e, "ECC repair: status readback");
     std::vector<uint32_t> damaged;
     for (uint32_t i = 0; i < nchunks; i++)
         if (status[i] == KCDC_ECC_DAMAGED) damaged.push_back(i);
@@ -689,7 +688,7 @@ extern "C" int kcdc_ecc_repair_chunks_device(const char* alg, int32_t overhead_p
     std::vector<uint64_t> lens(nchunks), blk_off(nchunks);
     if ((e = hipMemcpy(lens.data(), d_stored_lens, size_t(nchunks) * 8u, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(blk_off.data(), a.blk_off, size_t(nchunks) * 8u, hipMemcpyDeviceToHost)) != hipSuccess)
-        return hip_fail(e, "ECC repair: length readback");
+        return hip_error(e, "ECC repair: length readback");
 
     const EccParams& p = a.prm;
     std::vector<uint8_t> big(size_t(p.data) * p.parity), small(size_t(kEccSmallData) * kEccSmallParity);
@@ -712,7 +711,7 @@ extern "C" int kcdc_ecc_repair_chunks_device(const char* alg, int32_t overhead_p
             return set_error(-22, "ECC repair: not the workspace of this launch's decode call");
         masks.resize(size_t(g.blocks) * 8u);
         if ((e = hipMemcpy(masks.data(), a.masks + blk_off[c] * 8u, masks.size() * 4u, hipMemcpyDeviceToHost)) != hipSuccess)
-            return hip_fail(e, "ECC repair: mask readback");
+            return hip_error(e, "ECC repair: mask readback");
         uint32_t flags = 0;
         const size_t first_job = jobs.size();
         for (uint64_t b = 0; b < g.blocks && !(flags & 0x100u); b++) {
@@ -770,7 +769,7 @@ extern "C" int kcdc_ecc_repair_chunks_device(const char* alg, int32_t overhead_p
                            dim3(eccdev::kThreads), 0, st, a, d_fin);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = hip_fail(e, "ECC repair kernels");
+        if (e != hipSuccess) rc = hip_error(e, "ECC repair kernels");
     }
     if (d_coef) (void)hipFree(d_coef);
     if (d_idx) (void)hipFree(d_idx);

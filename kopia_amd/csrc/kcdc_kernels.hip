@@ -25,7 +25,8 @@
 //       whose min passes is re-run exactly; the earliest lane's candidate is the cut.
 //   split_batch_rk_kernel    the Rabin-Karp batch walk (two chains per lane).
 //   cand_scan_dma_kernel / cand_scan_rk_kernel, seg_prefix, compact, resolve   the long path.
-//   scan_first_kernel        one region's first candidate (streaming handle).
+//   scan_first_cp_kernel / scan_first_batch_cp_kernel / scan_server_kernel   a slice's first
+//       candidate (streaming handles).
 //   split_fixed_kernel       FIXED names (reads no data).
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,7 @@
 #include <vector>
 #include <string>
 
+#include "kcdc_hip.h"
 #include "kcdc_internal.h"
 
 namespace kcdc {
@@ -2765,43 +2767,85 @@ __global__ void split_fixed_kernel(BatchArgs a) {
     if (threadIdx.x == 0) a.counts[sid] = cnt;
 }
 
-// Streaming-handle support: first candidate in [lo, hi] of one aligned buffer.
+// Streaming-handle scans: the first candidate in [lo, hi] of one request, a slice of `len` bytes
+// (64 bytes of history first) in mapped host staging.  Copy, then scan, one 8-wave workgroup per
+// request: the bytes are copied into device scratch with 8 16-byte PCIe reads in flight per
+// thread (a load-store loop left one read per thread outstanding and cost ~2 us per 8 KiB), then
+// 8 waves scan 8 sub-ranges of [lo, hi] and the smallest first candidate wins.  One wave reading
+// 64 KiB of host memory itself was PCIe-latency bound (41 us per private scan, 54 us per group
+// launch).  Called by every thread of the workgroup; between two calls in one kernel the caller
+// puts a barrier (the per-wave results are rewritten).
+constexpr int kScanWaves = 8;  // 64 KiB of PCIe reads in flight; 2 waves per SIMD: its kernels need up to 253
+                               // VGPRs (`make asm`, build/asm/resource.txt), so 1,024 threads would spill
 template <int KIND>
-__global__ __launch_bounds__(kWave) void scan_first_kernel(BatchArgs a, const uint8_t* buf, int64_t len, int64_t lo,
-                                                            int64_t hi, int64_t* out) {
-    __shared__ HashSmem<KIND> sm;
-    fill_tables<KIND>(sm, a);
-    const int lane = threadIdx.x & (kWave - 1);
+__device__ __forceinline__ int64_t scan_request_cp(HashSmem<KIND>& sm, const BatchArgs& a, const uint8_t* src,
+                                                   uint8_t* scr, int64_t len, int64_t lo, int64_t hi) {
+    __shared__ int64_t wf[kScanWaves];
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    constexpr int kIn = 8;
+    constexpr int64_t kT = kScanWaves * kWave;
+    const int64_t n16 = len >> 4;
+    const u32x4* s16 = reinterpret_cast<const u32x4*>(src);
+    u32x4* d16 = reinterpret_cast<u32x4*>(scr);
+    for (int64_t b = 0; b < n16; b += kIn * kT) {
+        u32x4 v[kIn];
+#pragma unroll
+        for (int k = 0; k < kIn; k++) {
+            const int64_t i = b + k * kT + threadIdx.x;
+            if (i < n16) v[k] = __builtin_nontemporal_load(s16 + i);
+        }
+#pragma unroll
+        for (int k = 0; k < kIn; k++) {
+            const int64_t i = b + k * kT + threadIdx.x;
+            if (i < n16) d16[i] = v[k];
+        }
+    }
+    for (int64_t i = (n16 << 4) + threadIdx.x; i < len; i += kT) scr[i] = src[i];
+    __syncthreads();
+    asm volatile("buffer_inv sc0" ::: "memory");  // this CU's L1 may hold an earlier request's lines
     const auto hash = make_hash<KIND>(sm, a, lane);
-    const int64_t f = scan_region(hash, buf, 0, len, lo, hi, lane);
-    if (lane == 0) out[0] = f;
+    const int64_t span = hi - lo + 1, per = ((span + kScanWaves - 1) / kScanWaves + 63) & ~int64_t(63);
+    const int64_t mlo = lo + per * w, mhi = mlo + per - 1 < hi ? mlo + per - 1 : hi;
+    const int64_t f = mlo <= mhi ? scan_region(hash, scr, 0, len, mlo, mhi, lane) : -1;
+    if (lane == 0) wf[w] = f;
+    __syncthreads();
+    int64_t best = -1;
+    for (int k = 0; k < kScanWaves; k++)
+        if (wf[k] >= 0 && (best < 0 || wf[k] < best)) best = wf[k];
+    return best;
 }
 
-// Grouped streaming handles: one wave per request, request r = first candidate in [lo, hi]
-// of the buffer at base + off (256-byte aligned, `len` bytes, 64 bytes of history first).
 template <int KIND>
-__global__ __launch_bounds__(kWave) void scan_first_batch_kernel(BatchArgs a, const uint8_t* base,
-                                                                 const ScanReq* reqs, int64_t* out) {
+__global__ __launch_bounds__(kScanWaves * kWave) void scan_first_cp_kernel(BatchArgs a, const uint8_t* buf, int64_t len,
+                                                                           int64_t lo, int64_t hi, int64_t* out,
+                                                                           uint8_t* scratch) {
     __shared__ HashSmem<KIND> sm;
     fill_tables<KIND>(sm, a);
-    const int lane = threadIdx.x & (kWave - 1);
-    const auto hash = make_hash<KIND>(sm, a, lane);
+    const int64_t f = scan_request_cp<KIND>(sm, a, buf, scratch, len, lo, hi);
+    if (threadIdx.x == 0) out[0] = f;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kScanWaves * kWave) void scan_first_batch_cp_kernel(BatchArgs a, const uint8_t* base,
+                                                                                 const ScanReq* reqs, int64_t* out,
+                                                                                 uint8_t* scratch) {
+    __shared__ HashSmem<KIND> sm;
+    fill_tables<KIND>(sm, a);
     const ScanReq& r = reqs[blockIdx.x];
     const uint64_t off = uni64(r.off);
     const int64_t len = static_cast<int64_t>(uni64(static_cast<uint64_t>(r.len)));
     const int64_t lo = static_cast<int64_t>(uni64(static_cast<uint64_t>(r.lo)));
     const int64_t hi = static_cast<int64_t>(uni64(static_cast<uint64_t>(r.hi)));
-    const int64_t f = scan_region(hash, base + off, 0, len, lo, hi, lane);
-    if (lane == 0) out[blockIdx.x] = f;
+    const int64_t f = scan_request_cp<KIND>(sm, a, base + off, scratch + off, len, lo, hi);
+    if (threadIdx.x == 0) out[blockIdx.x] = f;
 }
 
 // Resident scan server for private streaming handles (kcdc_splitter_next): one workgroup
 // stays on the GPU while handles are busy and takes requests from a mailbox in fine-grained
 // (coherent) host memory, so a NextSplitPoint pays no kernel launch and no table fill.
-// Per request: all 512 threads copy the slice (mapped host staging) into device scratch
-// with every load in flight, then 8 waves scan 8 sub-ranges of [lo, hi] and the smallest
-// first candidate wins.  The kernel exits after kSrvIdle ticks without a request or
-// kSrvLife ticks in total (s_memrealtime, 100 MHz); the host relaunches it when needed.
+// Each request is one scan_request_cp.  The kernel exits after kSrvIdle ticks without a
+// request or kSrvLife ticks in total (s_memrealtime, 100 MHz); the host relaunches it when
+// needed.
 struct ServerMbox {
     uint64_t req_seq;  // host: incremented after the fields below are written
     uint64_t pad0[7];
@@ -2814,17 +2858,13 @@ struct ServerMbox {
 };
 constexpr uint64_t kSrvIdle = 200000;     // 2 ms
 constexpr uint64_t kSrvLife = 20000000;   // 200 ms: every server kernel is bounded
-constexpr int kSrvWaves = 8;  // 2 per SIMD: scan_region needs up to 219 VGPRs (1,024 threads spilled)
 
 template <int KIND>
-__global__ __launch_bounds__(kSrvWaves * kWave) void scan_server_kernel(BatchArgs a, ServerMbox* mb, uint8_t* scratch,
-                                                                        uint64_t served) {
+__global__ __launch_bounds__(kScanWaves * kWave) void scan_server_kernel(BatchArgs a, ServerMbox* mb, uint8_t* scratch,
+                                                                         uint64_t served) {
     __shared__ HashSmem<KIND> sm;
-    __shared__ int64_t wave_first[kSrvWaves];
     __shared__ uint64_t cmd[5];
     fill_tables<KIND>(sm, a);
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-    const auto hash0 = make_hash<KIND>(sm, a, lane);
     const uint64_t t0 = wall_clock64();
     uint64_t last = t0;
     for (;;) {
@@ -2854,47 +2894,15 @@ __global__ __launch_bounds__(kSrvWaves * kWave) void scan_server_kernel(BatchArg
         const uint8_t* src = reinterpret_cast<const uint8_t*>(cmd[1]);
         const int64_t len = static_cast<int64_t>(cmd[2]), lo = static_cast<int64_t>(cmd[3]),
                       hi = static_cast<int64_t>(cmd[4]);
-        // the slice -> device scratch (the staging is 256-byte aligned; len <= the scratch).
         // One system-scope acquire per request (not per poll): no line of the staging, which
-        // the host rewrites between requests, may be served from a cache.
+        // the host rewrites between requests, may be served from a cache.  (The staging is
+        // 256-byte aligned; len <= the scratch.)
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        // 8 loads in flight per thread (64 KiB per round over PCIe), then their stores: a
-        // load-store loop left one 16-byte PCIe read per thread outstanding and cost ~2 us per 8 KiB
-        const int64_t n16 = len >> 4;
-        constexpr int kIn = 8;  // 16-byte PCIe reads in flight per thread while copying a request's slice
-        constexpr int64_t kT = kSrvWaves * kWave;
-        const u32x4* s16 = reinterpret_cast<const u32x4*>(src);
-        u32x4* d16 = reinterpret_cast<u32x4*>(scratch);
-        for (int64_t base = 0; base < n16; base += kIn * kT) {
-            u32x4 v[kIn];
-#pragma unroll
-            for (int k = 0; k < kIn; k++) {
-                const int64_t i = base + k * kT + threadIdx.x;
-                if (i < n16) v[k] = __builtin_nontemporal_load(s16 + i);
-            }
-#pragma unroll
-            for (int k = 0; k < kIn; k++) {
-                const int64_t i = base + k * kT + threadIdx.x;
-                if (i < n16) d16[i] = v[k];
-            }
-        }
-        for (int64_t i = (n16 << 4) + threadIdx.x; i < len; i += kT) scratch[i] = src[i];
-        // Every reader of the scratch is a wave of this workgroup: after the barrier (which waits
-        // for the stores) only this CU's vector L1 may still hold the previous request's lines,
-        // so invalidate just that (an agent-scope fence would also write back and invalidate
-        // the L2 on every request).
-        __syncthreads();
-        asm volatile("buffer_inv sc0" ::: "memory");
-        const int64_t span = hi - lo + 1, per = ((span + kSrvWaves - 1) / kSrvWaves + 63) & ~int64_t(63);
-        const int64_t mlo = lo + per * w, mhi = mlo + per - 1 < hi ? mlo + per - 1 : hi;
-        int64_t f = -1;
-        if (mlo <= mhi) f = scan_region(hash0, scratch, 0, len, mlo, mhi, lane);
-        if (lane == 0) wave_first[w] = f;
-        __syncthreads();
+        // Every reader of the scratch is a wave of this workgroup: scan_request_cp invalidates
+        // just this CU's vector L1 after its copy (an agent-scope fence would also write back
+        // and invalidate the L2 on every request).
+        const int64_t best = scan_request_cp<KIND>(sm, a, src, scratch, len, lo, hi);
         if (threadIdx.x == 0) {
-            int64_t best = -1;
-            for (int k = 0; k < kSrvWaves; k++)
-                if (wave_first[k] >= 0 && (best < 0 || wave_first[k] < best)) best = wave_first[k];
             // result, then (after it has completed) the sequence number the host waits for; a
             // release at system scope would write back the whole L2 first
             __hip_atomic_store(&mb->result, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -2903,76 +2911,8 @@ __global__ __launch_bounds__(kSrvWaves * kWave) void scan_server_kernel(BatchArg
         }
         served = sq;
         last = wall_clock64();
-        __syncthreads();
+        __syncthreads();  // thread 0 rewrites cmd[], and the next request the per-wave results
     }
-}
-
-// Copy-then-scan form of the scans above, one 8-wave workgroup per request: the request's
-// bytes (mapped host staging) are copied into device scratch with 8 16-byte PCIe reads in
-// flight per thread, then 8 waves scan 8 sub-ranges of [lo, hi].  One wave reading 64 KiB of
-// host memory itself was PCIe-latency bound (41 us per private scan, 54 us per group launch).
-constexpr int kCpWaves = 8;  // 64 KiB of PCIe reads in flight; 2 waves per SIMD (scan_region <= 235 VGPRs)
-template <int KIND>
-__device__ __forceinline__ int64_t scan_request_cp(HashSmem<KIND>& sm, const BatchArgs& a, const uint8_t* src,
-                                                   uint8_t* scr, int64_t len, int64_t lo, int64_t hi) {
-    __shared__ int64_t wf[kCpWaves];
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-    constexpr int kIn = 8;
-    constexpr int64_t kT = kCpWaves * kWave;
-    const int64_t n16 = len >> 4;
-    const u32x4* s16 = reinterpret_cast<const u32x4*>(src);
-    u32x4* d16 = reinterpret_cast<u32x4*>(scr);
-    for (int64_t b = 0; b < n16; b += kIn * kT) {
-        u32x4 v[kIn];
-#pragma unroll
-        for (int k = 0; k < kIn; k++) {
-            const int64_t i = b + k * kT + threadIdx.x;
-            if (i < n16) v[k] = __builtin_nontemporal_load(s16 + i);
-        }
-#pragma unroll
-        for (int k = 0; k < kIn; k++) {
-            const int64_t i = b + k * kT + threadIdx.x;
-            if (i < n16) d16[i] = v[k];
-        }
-    }
-    for (int64_t i = (n16 << 4) + threadIdx.x; i < len; i += kT) scr[i] = src[i];
-    __syncthreads();
-    asm volatile("buffer_inv sc0" ::: "memory");  // this CU's L1 may hold an earlier request's lines
-    const auto hash = make_hash<KIND>(sm, a, lane);
-    const int64_t span = hi - lo + 1, per = ((span + kCpWaves - 1) / kCpWaves + 63) & ~int64_t(63);
-    const int64_t mlo = lo + per * w, mhi = mlo + per - 1 < hi ? mlo + per - 1 : hi;
-    const int64_t f = mlo <= mhi ? scan_region(hash, scr, 0, len, mlo, mhi, lane) : -1;
-    if (lane == 0) wf[w] = f;
-    __syncthreads();
-    int64_t best = -1;
-    for (int k = 0; k < kCpWaves; k++)
-        if (wf[k] >= 0 && (best < 0 || wf[k] < best)) best = wf[k];
-    return best;
-}
-
-template <int KIND>
-__global__ __launch_bounds__(kCpWaves * kWave) void scan_first_cp_kernel(BatchArgs a, const uint8_t* buf, int64_t len,
-                                                                         int64_t lo, int64_t hi, int64_t* out,
-                                                                         uint8_t* scratch) {
-    __shared__ HashSmem<KIND> sm;
-    fill_tables<KIND>(sm, a);
-    const int64_t f = scan_request_cp<KIND>(sm, a, buf, scratch, len, lo, hi);
-    if (threadIdx.x == 0) out[0] = f;
-}
-
-template <int KIND>
-__global__ __launch_bounds__(kCpWaves * kWave) void scan_first_batch_cp_kernel(BatchArgs a, const uint8_t* base,
-                                                                               const ScanReq* reqs, int64_t* out,
-                                                                               uint8_t* scratch) {
-    __shared__ HashSmem<KIND> sm;
-    fill_tables<KIND>(sm, a);
-    const ScanReq& r = reqs[blockIdx.x];
-    const uint64_t off = uni64(r.off);
-    const int64_t len = static_cast<int64_t>(uni64(static_cast<uint64_t>(r.len)));
-    const int64_t lo = static_cast<int64_t>(uni64(static_cast<uint64_t>(r.lo)));
-    const int64_t hi = static_cast<int64_t>(uni64(static_cast<uint64_t>(r.hi)));
-    const int64_t f = scan_request_cp<KIND>(sm, a, base + off, scratch + off, len, lo, hi);
-    if (threadIdx.x == 0) out[blockIdx.x] = f;
 }
 
 // ------------------------------------------------------ synthetic streams
@@ -3055,6 +2995,44 @@ __device__ __forceinline__ uint32_t long_stream_of(const LongArgs& g, int64_t se
     return lo;
 }
 
+// Global segment `seg` as its scanning wave sees it (wave-uniform): its stream, the segment's
+// first coordinate cs and the stream's coordinates [lo, hi] inside it.
+struct Seg {
+    const uint8_t* abase;
+    int64_t off0, n, cs, lo, hi;
+};
+__device__ __forceinline__ Seg long_seg_of(const LongArgs& g, int64_t seg) {
+    const LongStream& S = g.streams[long_stream_of(g, seg)];
+    Seg q;
+    q.off0 = static_cast<int64_t>(uni64(static_cast<uint64_t>(S.off0)));
+    q.n = static_cast<int64_t>(uni64(static_cast<uint64_t>(S.n)));
+    q.abase = reinterpret_cast<const uint8_t*>(uni64(reinterpret_cast<uint64_t>(S.abase)));
+    q.cs = (seg - static_cast<int64_t>(uni64(static_cast<uint64_t>(S.seg0)))) * kSegBytes;
+    q.lo = q.cs > q.off0 ? q.cs : q.off0;
+    q.hi = (q.cs + kSegBytes < q.off0 + q.n ? q.cs + kSegBytes : q.off0 + q.n) - 1;
+    return q;
+}
+
+// Record segment `seg`: lane l found nf candidates (kSegK + 1: more than kSegK) at offsets
+// found[] from the segment start, lanes in position order.  Stores the segment's first kSegK
+// candidates (positions from the stream start) and its count with the truncation flag.
+__device__ __forceinline__ void long_seg_record(const LongArgs& g, int64_t seg, const Seg& q, int lane, int nf,
+                                                const uint32_t (&found)[kSegK]) {
+    // exclusive prefix of per-lane counts (lane segments are in position order)
+    int incl = nf;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    const int tot = __shfl(incl, kWave - 1);
+    const int pre = incl - nf;
+    for (int j = 0; j < nf && j < kSegK; j++)
+        if (pre + j < kSegK) g.seg_cand[seg * kSegK + pre + j] = static_cast<uint64_t>(q.cs - q.off0) + found[j];
+    if (lane == 0)
+        g.seg_cnt[seg] = (tot > kSegK ? 0x80000000u : 0u) | static_cast<uint32_t>(tot < kSegK ? tot : kSegK);
+}
+
 // Rabin-Karp candidate scan of the long path on split_batch_rk_kernel's tile walk (two
 // chains per lane, alternating 128-byte line fills, outx[] folding): one 128 KiB segment per
 // tile, persistent grid-stride over the segments of every stream of the launch, the next
@@ -3068,34 +3046,19 @@ __global__ __launch_bounds__(kRkWaves * kWave, kRkWaves / 4) void cand_scan_rk_k
     uint8_t* sl = smslots.b[wave][0];
     const uint32_t sl32 = lds_addr(sl);
     const int64_t nw = static_cast<int64_t>(gridDim.x) * kRkWaves;
-    struct Seg {
-        const uint8_t* abase;
-        int64_t off0, n, cs, lo, hi;
-    };
-    auto seg_of = [&](int64_t seg) {
-        const LongStream& S = g.streams[long_stream_of(g, seg)];
-        Seg q;
-        q.off0 = static_cast<int64_t>(uni64(static_cast<uint64_t>(S.off0)));
-        q.n = static_cast<int64_t>(uni64(static_cast<uint64_t>(S.n)));
-        q.abase = reinterpret_cast<const uint8_t*>(uni64(reinterpret_cast<uint64_t>(S.abase)));
-        q.cs = (seg - static_cast<int64_t>(uni64(static_cast<uint64_t>(S.seg0)))) * kSegBytes;
-        q.lo = q.cs > q.off0 ? q.cs : q.off0;
-        q.hi = (q.cs + kSegBytes < q.off0 + q.n ? q.cs + kSegBytes : q.off0 + q.n) - 1;
-        return q;
-    };
     auto issue = [&](const Seg& q) {
         const RkGeom t = rk_geom(q.cs, q.hi, q.abase, q.off0, q.off0 + q.n);
         rk_dma_warm(t.ld, sl32, q.cs, t.L, lane);
     };
     int64_t seg = static_cast<int64_t>(blockIdx.x) * kRkWaves + wave;
     if (seg >= g.nseg) return;
-    Seg q = seg_of(seg);
+    Seg q = long_seg_of(g, seg);
     issue(q);
     for (;;) {
         const int64_t nseg_next = seg + nw;
         const bool has_next = nseg_next < g.nseg;
         Seg qn = q;
-        if (has_next) qn = seg_of(nseg_next);
+        if (has_next) qn = long_seg_of(g, nseg_next);
         const RkGeom t = rk_geom(q.cs, q.hi, q.abase, q.off0, q.off0 + q.n);
         uint32_t ha, la, hb, lb, pa[16], pb[16];
         {
@@ -3160,18 +3123,7 @@ __global__ __launch_bounds__(kRkWaves * kWave, kRkWaves / 4) void cand_scan_rk_k
                 if (j >= nas && k == j - nas) v = base_b + ((fb[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
             found[j] = v;
         }
-        int incl = nf;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
-        const int tot = __shfl(incl, kWave - 1);
-        const int pre = incl - nf;
-        for (int j = 0; j < nf && j < kSegK; j++)
-            if (pre + j < kSegK) g.seg_cand[seg * kSegK + pre + j] = static_cast<uint64_t>(q.cs - q.off0) + found[j];
-        if (lane == 0)
-            g.seg_cnt[seg] = (tot > kSegK ? 0x80000000u : 0u) | static_cast<uint32_t>(tot < kSegK ? tot : kSegK);
+        long_seg_record(g, seg, q, lane, nf, found);
         if (!has_next) break;
         seg = nseg_next;
         q = qn;
@@ -3203,21 +3155,6 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void cand_scan_dm
     const uint32_t sl32 = lds_addr(sl), wl32 = lds_addr(wl);
     const uint32_t lim = TOP ? a.buz_lim : 0u;
     const int64_t nw = static_cast<int64_t>(gridDim.x) * kDmaWaves;
-    struct Seg {
-        const uint8_t* abase;
-        int64_t off0, n, cs, lo, hi;
-    };
-    auto seg_of = [&](int64_t seg) {
-        const LongStream& S = g.streams[long_stream_of(g, seg)];
-        Seg q;
-        q.off0 = static_cast<int64_t>(uni64(static_cast<uint64_t>(S.off0)));
-        q.n = static_cast<int64_t>(uni64(static_cast<uint64_t>(S.n)));
-        q.abase = reinterpret_cast<const uint8_t*>(uni64(reinterpret_cast<uint64_t>(S.abase)));
-        q.cs = (seg - static_cast<int64_t>(uni64(static_cast<uint64_t>(S.seg0)))) * kSegBytes;
-        q.lo = q.cs > q.off0 ? q.cs : q.off0;
-        q.hi = (q.cs + kSegBytes < q.off0 + q.n ? q.cs + kSegBytes : q.off0 + q.n) - 1;
-        return q;
-    };
     auto issue = [&](const Seg& q) {
         const TileGeom t = tile_geom(q.cs, q.hi, q.abase, q.off0, q.off0 + q.n);
         dma_piece(t.ld, t.ld.tb, wl32, q.cs, t.L, -1, lane);
@@ -3225,13 +3162,13 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void cand_scan_dm
     };
     int64_t seg = static_cast<int64_t>(blockIdx.x) * kDmaWaves + wave;
     if (seg >= g.nseg) return;
-    Seg q = seg_of(seg);
+    Seg q = long_seg_of(g, seg);
     issue(q);
     for (;;) {
         const int64_t nseg_next = seg + nw;
         const bool has_next = nseg_next < g.nseg;
         Seg qn = q;
-        if (has_next) qn = seg_of(nseg_next);
+        if (has_next) qn = long_seg_of(g, nseg_next);
         const TileGeom t = tile_geom(q.cs, q.hi, q.abase, q.off0, q.off0 + q.n);
         const int64_t c0 = q.cs + lane * t.L;
         {
@@ -3277,19 +3214,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void cand_scan_dm
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), visible to the waitcnt pass
             }
         }
-        // exclusive prefix of per-lane counts (lane segments are in position order)
-        int incl = nf;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
-        const int tot = __shfl(incl, kWave - 1);
-        const int pre = incl - nf;
-        for (int j = 0; j < nf && j < kSegK; j++)
-            if (pre + j < kSegK) g.seg_cand[seg * kSegK + pre + j] = static_cast<uint64_t>(q.cs - q.off0) + found[j];
-        if (lane == 0)
-            g.seg_cnt[seg] = (tot > kSegK ? 0x80000000u : 0u) | static_cast<uint32_t>(tot < kSegK ? tot : kSegK);
+        long_seg_record(g, seg, q, lane, nf, found);
         if (!has_next) break;
         seg = nseg_next;
         q = qn;
@@ -3670,8 +3595,6 @@ unsigned g_queue_next[kMaxDevices];
 // serialised per device only, so threads driving different devices never wait on each other.
 std::mutex g_dev_mu[kMaxDevices];
 
-int hip_fail(hipError_t e, const char* what) { return set_error(-5, std::string(what) + ": " + hipGetErrorString(e)); }
-
 // Test hooks (kcdc_test_set, include/kcdc.h "testing"): read by every later launch.
 struct TestKnobs {
     uint32_t spin_cap = 0;     // 0: dev::kSpinCap
@@ -3781,11 +3704,10 @@ const DeviceTables* device_tables(int device, int* err) {
     std::lock_guard<std::mutex> lk(g_dev_mu[device]);
     if (g_dev_ready[device]) return &g_dev_tables[device];
     const Tables& T = tables();
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    hipError_t e = hipSetDevice(device);
+    DeviceGuard dg(device);
+    hipError_t e = dg.err;
     if (e != hipSuccess) {
-        *err = hip_fail(e, "hipSetDevice");
+        *err = hip_error(e, "hipSetDevice");
         return nullptr;
     }
     DeviceTables d;
@@ -3798,9 +3720,8 @@ const DeviceTables* device_tables(int device, int* err) {
     if (e == hipSuccess) e = hipMemcpy(d.buz, T.buz, sizeof(T.buz), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d.rk_out, T.rk_out, sizeof(T.rk_out), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d.rk_mod, T.rk_mod, sizeof(T.rk_mod), hipMemcpyHostToDevice);
-    (void)hipSetDevice(prev);
     if (e != hipSuccess) {
-        *err = hip_fail(e, "table upload");
+        *err = hip_error(e, "table upload");
         return nullptr;
     }
     g_dev_tables[device] = d;
@@ -3913,9 +3834,7 @@ int queue_slot(int device, hipStream_t st, size_t bytes, QueueWs*& out) {
     QueueWs& q = g_qws[device][slot];
     const bool same_stream = q.used && q.last == st;  // stream order covers the previous launch
     if (q.bytes < bytes) {
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
+        DeviceGuard dg(device);
         char* nb = nullptr;
         size_t nbytes = bytes > 2 * q.bytes ? bytes : 2 * q.bytes;
         // Stream-ordered: a plain hipFree synchronises the whole device, so a launch that
@@ -3926,26 +3845,41 @@ int queue_slot(int device, hipStream_t st, size_t bytes, QueueWs*& out) {
             if (q.done) e = hipStreamWaitEvent(st, q.done, 0);
             if (e == hipSuccess) e = hipFreeAsync(q.base, st);
         }
-        (void)hipSetDevice(prev);
-        if (e != hipSuccess) return hip_fail(e, "queue workspace");
+        if (e != hipSuccess) return hip_error(e, "queue workspace");
         q.base = nb;
         q.bytes = nbytes;
     }
     if (!q.done) {
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
+        DeviceGuard dg(device);
         const hipError_t e = hipEventCreateWithFlags(&q.done, hipEventDisableTiming | hipEventDisableSystemFence);
-        (void)hipSetDevice(prev);
-        if (e != hipSuccess) return hip_fail(e, "queue workspace event");
+        if (e != hipSuccess) return hip_error(e, "queue workspace event");
     } else if (!same_stream) {
         const hipError_t e = hipStreamWaitEvent(st, q.done, 0);
-        if (e != hipSuccess) return hip_fail(e, "queue workspace wait");
+        if (e != hipSuccess) return hip_error(e, "queue workspace wait");
     }
     q.last = st;
     q.used = true;
     out = &q;
     return 0;
+}
+
+// launch(kind) with the hash kind of a rolling splitter as a compile-time constant: the KIND
+// argument of the kernel templates is decltype(kind)::value.  FIXED splitters read no data.
+template <class Launch>
+int with_kind(const Algo& algo, const char* what, Launch launch) {
+    if (algo.kind == kBuzhash)
+        launch(std::integral_constant<int, kBuzhash>{});
+    else if (algo.kind == kRabinKarp)
+        launch(std::integral_constant<int, kRabinKarp>{});
+    else
+        return set_error(-22, std::string(what) + ": FIXED splitters read no data");
+    return 0;
+}
+
+// After a kernel launch: 0, or the launch error recorded under `what`.
+int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_error(e, what);
 }
 }  // namespace
 
@@ -4015,39 +3949,26 @@ int launch_split_batch(const Algo& algo, const SplitArgs& s, int device, void* s
             hipLaunchKernelGGL(dev::poison_counts_kernel, dim3(std::min<unsigned>((s.nstreams + 255) / 256, 256u)),
                                dim3(256), 0, st, a);
         const hipError_t er = hipEventRecord(q->done, st);
-        if (er != hipSuccess) return hip_fail(er, "queue workspace record");
+        if (er != hipSuccess) return hip_error(er, "queue workspace record");
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "split kernel launch");
+    return launched("split kernel launch");
 }
 
 int launch_scan_first(const Algo& algo, const uint8_t* d_buf, uint64_t len, int64_t lo, int64_t hi, int64_t* d_out,
                       int device, void* stream, uint8_t* d_scratch) {
+    if (!d_scratch) return set_error(-22, "scan_first: no scratch buffer");
     int err = 0;
     const DeviceTables* t = device_tables(device, &err);
     if (!t) return err;
     dev::BatchArgs a = base_args(algo, *t);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (d_scratch && (algo.kind == kBuzhash || algo.kind == kRabinKarp)) {
-        if (algo.kind == kBuzhash)
-            hipLaunchKernelGGL(dev::scan_first_cp_kernel<kBuzhash>, dim3(1), dim3(dev::kCpWaves * dev::kWave), 0, st, a,
-                               d_buf, static_cast<int64_t>(len), lo, hi, d_out, d_scratch);
-        else
-            hipLaunchKernelGGL(dev::scan_first_cp_kernel<kRabinKarp>, dim3(1), dim3(dev::kCpWaves * dev::kWave), 0, st,
-                               a, d_buf, static_cast<int64_t>(len), lo, hi, d_out, d_scratch);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "scan kernel launch");
-    }
-    if (algo.kind == kBuzhash)
-        hipLaunchKernelGGL(dev::scan_first_kernel<kBuzhash>, dim3(1), dim3(dev::kWave), 0, st, a, d_buf,
-                           static_cast<int64_t>(len), lo, hi, d_out);
-    else if (algo.kind == kRabinKarp)
-        hipLaunchKernelGGL(dev::scan_first_kernel<kRabinKarp>, dim3(1), dim3(dev::kWave), 0, st, a, d_buf,
-                           static_cast<int64_t>(len), lo, hi, d_out);
-    else
-        return set_error(-22, "scan_first: FIXED splitters read no data");
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "scan kernel launch");
+    if (const int rc = with_kind(algo, "scan_first", [&](auto kind) {
+            hipLaunchKernelGGL(dev::scan_first_cp_kernel<decltype(kind)::value>, dim3(1),
+                               dim3(dev::kScanWaves * dev::kWave), 0, st, a, d_buf, static_cast<int64_t>(len), lo, hi,
+                               d_out, d_scratch);
+        }))
+        return rc;
+    return launched("scan kernel launch");
 }
 
 // ---- resident scan server (host side): one per (device, hash kind)
@@ -4070,14 +3991,12 @@ std::atomic<uint64_t> g_srv_served{0};  // requests answered by a server (kcdc_t
 
 int srv_launch(ScanServer& sv, const Algo& algo, const DeviceTables& t) {
     dev::BatchArgs a = base_args(algo, t);
-    if (algo.kind == kBuzhash)
-        hipLaunchKernelGGL(dev::scan_server_kernel<kBuzhash>, dim3(1), dim3(dev::kSrvWaves * dev::kWave), 0, sv.st, a,
-                           sv.d, sv.scratch, sv.seq - 1);
-    else
-        hipLaunchKernelGGL(dev::scan_server_kernel<kRabinKarp>, dim3(1), dim3(dev::kSrvWaves * dev::kWave), 0, sv.st, a,
-                           sv.d, sv.scratch, sv.seq - 1);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "scan server launch");
+    int rc = with_kind(algo, "scan server", [&](auto kind) {
+        hipLaunchKernelGGL(dev::scan_server_kernel<decltype(kind)::value>, dim3(1), dim3(dev::kScanWaves * dev::kWave), 0,
+                           sv.st, a, sv.d, sv.scratch, sv.seq - 1);
+    });
+    if (!rc) rc = launched("scan server launch");
+    if (rc) return rc;
     sv.launched = true;
     return 0;
 }
@@ -4109,7 +4028,7 @@ int server_scan_first(const Algo& algo, const uint8_t* d_stage, uint64_t len, in
     }
     if (len > sv.cap) {  // grow the scratch: the previous server must be gone first
         if (sv.launched) {
-            if (hipStreamSynchronize(sv.st) != hipSuccess) return hip_fail(hipGetLastError(), "scan server sync");
+            if (hipStreamSynchronize(sv.st) != hipSuccess) return hip_error(hipGetLastError(), "scan server sync");
             sv.launched = false;
         }
         if (sv.scratch) (void)hipFree(sv.scratch);
@@ -4157,32 +4076,19 @@ int server_scan_first(const Algo& algo, const uint8_t* d_stage, uint64_t len, in
 
 int launch_scan_first_batch(const Algo& algo, const uint8_t* d_base, const ScanReq* d_reqs, uint32_t n, int64_t* d_out,
                             int device, void* stream, uint8_t* d_scratch) {
+    if (!d_scratch) return set_error(-22, "scan_first: no scratch buffer");
     int err = 0;
     const DeviceTables* t = device_tables(device, &err);
     if (!t) return err;
     if (n == 0) return 0;
     dev::BatchArgs a = base_args(algo, *t);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (d_scratch && (algo.kind == kBuzhash || algo.kind == kRabinKarp)) {
-        if (algo.kind == kBuzhash)
-            hipLaunchKernelGGL(dev::scan_first_batch_cp_kernel<kBuzhash>, dim3(n), dim3(dev::kCpWaves * dev::kWave), 0,
-                               st, a, d_base, d_reqs, d_out, d_scratch);
-        else
-            hipLaunchKernelGGL(dev::scan_first_batch_cp_kernel<kRabinKarp>, dim3(n), dim3(dev::kCpWaves * dev::kWave), 0,
-                               st, a, d_base, d_reqs, d_out, d_scratch);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "scan kernel launch");
-    }
-    if (algo.kind == kBuzhash)
-        hipLaunchKernelGGL(dev::scan_first_batch_kernel<kBuzhash>, dim3(n), dim3(dev::kWave), 0, st, a, d_base, d_reqs,
-                           d_out);
-    else if (algo.kind == kRabinKarp)
-        hipLaunchKernelGGL(dev::scan_first_batch_kernel<kRabinKarp>, dim3(n), dim3(dev::kWave), 0, st, a, d_base,
-                           d_reqs, d_out);
-    else
-        return set_error(-22, "scan_first: FIXED splitters read no data");
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "scan kernel launch");
+    if (const int rc = with_kind(algo, "scan_first", [&](auto kind) {
+            hipLaunchKernelGGL(dev::scan_first_batch_cp_kernel<decltype(kind)::value>, dim3(n),
+                               dim3(dev::kScanWaves * dev::kWave), 0, st, a, d_base, d_reqs, d_out, d_scratch);
+        }))
+        return rc;
+    return launched("scan kernel launch");
 }
 
 int launch_fill_prng(uint8_t* d_data, uint64_t stride, uint64_t stream_len, uint32_t nstreams, uint64_t seed,
@@ -4192,8 +4098,7 @@ int launch_fill_prng(uint8_t* d_data, uint64_t stride, uint64_t stream_len, uint
     if (nstreams == 0 || stream_len == 0) return 0;
     hipLaunchKernelGGL(dev::fill_prng_kernel, dim3(4096), dim3(256), 0, static_cast<hipStream_t>(stream), d_data,
                        stride, stream_len, nstreams, seed, first_sid);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "fill kernel launch");
+    return launched("fill kernel launch");
 }
 
 namespace {
@@ -4304,7 +4209,7 @@ int launch_split_long_multi(const Algo& algo, uint32_t m, const uint8_t* const* 
         g.levels = L.levels;
     }
     hipError_t e = hipMemcpyAsync(w + L.off_streams, hs.data(), m * sizeof(dev::LongStream), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(e, "long-stream descriptors");
+    if (e != hipSuccess) return hip_error(e, "long-stream descriptors");
     dev::BatchArgs a = base_args(algo, *t);
     const int64_t mn = static_cast<int64_t>(algo.min_size()), mx = static_cast<int64_t>(algo.max_size());
     if (nseg > 0) {
@@ -4330,16 +4235,15 @@ int launch_split_long_multi(const Algo& algo, uint32_t m, const uint8_t* const* 
     if (g.serial) {  // streams it cannot take (truncated segments) stay flagged for resolve_kernel
         if (nseg == 0) {
             e = hipMemsetAsync(w + L.off_total, 0, sizeof(uint64_t), st);
-            if (e != hipSuccess) return hip_fail(e, "long-stream total");
+            if (e != hipSuccess) return hip_error(e, "long-stream total");
         }
         hipLaunchKernelGGL(dev::resolve_par_kernel, dim3(m), dim3(1024), 0, st, g, mn, mx);
     }
-    if (algo.kind == kBuzhash)
-        hipLaunchKernelGGL(dev::resolve_kernel<kBuzhash>, dim3(m), dim3(dev::kWave), 0, st, a, g, mn, mx);
-    else
-        hipLaunchKernelGGL(dev::resolve_kernel<kRabinKarp>, dim3(m), dim3(dev::kWave), 0, st, a, g, mn, mx);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "long-stream kernel launch");
+    int rc = with_kind(algo, "long-stream path", [&](auto kind) {
+        hipLaunchKernelGGL(dev::resolve_kernel<decltype(kind)::value>, dim3(m), dim3(dev::kWave), 0, st, a, g, mn, mx);
+    });
+    if (!rc) rc = launched("long-stream kernel launch");
+    if (rc) return rc;
     if (g_test.long_stat) {  // test hook: which resolver took each stream (kcdc_test_long_stat)
         if (m > g_test.long_serial_cap) {
             if (g_test.long_serial) {  // (an earlier launch's copy may still be in flight)
@@ -4349,12 +4253,12 @@ int launch_split_long_multi(const Algo& algo, uint32_t m, const uint8_t* const* 
             g_test.long_serial = nullptr;
             g_test.long_serial_cap = 0;
             e = hipHostMalloc(reinterpret_cast<void**>(&g_test.long_serial), m * sizeof(uint32_t), hipHostMallocDefault);
-            if (e != hipSuccess) return hip_fail(e, "long-stream statistics");
+            if (e != hipSuccess) return hip_error(e, "long-stream statistics");
             g_test.long_serial_cap = m;
         }
         // stream-ordered after resolve_par_kernel, before the caller can release the workspace
         e = hipMemcpyAsync(g_test.long_serial, w + L.off_serial, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) return hip_fail(e, "long-stream statistics");
+        if (e != hipSuccess) return hip_error(e, "long-stream statistics");
         g_test.long_streams = m;
         g_test.long_seen = true;
     }
@@ -4418,13 +4322,10 @@ extern "C" int64_t kcdc_test_queue_stat(int32_t key) {
                    : key == 10 ? dev::kQHT : key == 11 ? dev::kQHT + 1 : -1;
     if (word < 0) return set_error(-22, "unknown queue statistic");
     if (!g_test.last_ws) return set_error(-22, "no pipelined batch launch yet");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(g_test.last_dev);
+    DeviceGuard dg(g_test.last_dev);
     uint32_t v = 0;
     const hipError_t e = hipMemcpy(&v, g_test.last_ws + 4 * word, 4, hipMemcpyDeviceToHost);
-    (void)hipSetDevice(prev);
-    return e == hipSuccess ? static_cast<int64_t>(v) : hip_fail(e, "queue statistic");
+    return e == hipSuccess ? static_cast<int64_t>(v) : hip_error(e, "queue statistic");
 }
 
 // Test hook: what batch_plan gives a launch of `nstreams` streams of splitter `name` on device 0
@@ -4450,12 +4351,9 @@ extern "C" int kcdc_test_batch_plan(const char* name, uint32_t nstreams, uint32_
 // help slots) to host memory, for post-mortems of a launch (tools/batch_probe.py).
 extern "C" int kcdc_test_ws_copy(void* dst, uint64_t off, uint64_t n) {
     if (!g_test.last_ws) return set_error(-22, "no pipelined batch launch yet");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(g_test.last_dev);
+    DeviceGuard dg(g_test.last_dev);
     const hipError_t e = hipMemcpy(dst, g_test.last_ws + off, n, hipMemcpyDeviceToHost);
-    (void)hipSetDevice(prev);
-    return e == hipSuccess ? 0 : hip_fail(e, "workspace copy");
+    return e == hipSuccess ? 0 : hip_error(e, "workspace copy");
 }
 
 extern "C" int kcdc_test_occupy(uint32_t nwg, uint32_t usec, void* stream) {
@@ -4463,15 +4361,15 @@ extern "C" int kcdc_test_occupy(uint32_t nwg, uint32_t usec, void* stream) {
     if (usec > 10u * 1000u * 1000u) return set_error(-22, "occupy: at most 10 s");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dev::occupy_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return hip_fail(e, "occupy attribute");
+    if (e != hipSuccess) return hip_error(e, "occupy attribute");
     uint32_t* sink = nullptr;
     e = hipMallocAsync(reinterpret_cast<void**>(&sink), 4, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "occupy sink");
+    if (e != hipSuccess) return hip_error(e, "occupy sink");
     hipLaunchKernelGGL(dev::occupy_kernel, dim3(nwg), dim3(64), 160 * 1024, static_cast<hipStream_t>(stream),
                        static_cast<uint64_t>(usec) * 100u, sink);
     e = hipGetLastError();
     (void)hipFreeAsync(sink, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : hip_fail(e, "occupy launch");
+    return e == hipSuccess ? 0 : hip_error(e, "occupy launch");
 }
 
 }  // namespace kcdc

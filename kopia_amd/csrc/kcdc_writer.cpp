@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/kcdc.h"
+#include "kcdc_hip.h"
 #include "kcdc_internal.h"
 
 using namespace kcdc;
@@ -46,19 +47,6 @@ constexpr size_t kBlock = 4u << 20;    // pinned staging block
 constexpr size_t kSlabBlocks = 8;      // blocks per pinned allocation
 constexpr uint64_t kHist = 64;         // window history kept before a writer's last final cut
 constexpr uint32_t kTask = 64u << 10;  // gather: bytes per workgroup
-
-int hip_err(hipError_t e, const char* what) { return set_error(KCDC_EIO, std::string(what) + ": " + hipGetErrorString(e)); }
-
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // One gather piece: len bytes from pinned host memory (device-visible) to a writer's arena;
 // src and dst are congruent mod 16.
@@ -228,7 +216,7 @@ struct BwDev {
     size_t peak_open = 0;  // (mu) most writers open at once since the cache was last trimmed
     size_t keep_arenas() const { return peak_open; }
     void trim_arenas() {  // mu held; the cached pairs are idle (their writers' rounds completed)
-        Guard g(device);
+        DeviceGuard g(device);
         for (auto& ar : arenas) {
             (void)hipFree(ar.first);
             (void)hipFree(ar.second);
@@ -371,7 +359,7 @@ struct BwDev {
             hth.join();
         }
         if (algo->kind == kFixed) return;
-        Guard g(device);
+        DeviceGuard g(device);
         for (uint8_t* s : slabs) (void)hipHostFree(s);
         for (auto& a : arenas) {
             (void)hipFree(a.first);
@@ -423,7 +411,7 @@ struct BwDev {
         // staging peak grows in steps of many blocks when many writers are open
         pool_misses++;
         void* p = nullptr;
-        Guard g(device);
+        DeviceGuard g(device);
         if (hipHostMalloc(&p, kSlabBlocks * kBlock, hipHostMallocDefault) != hipSuccess) return nullptr;
         uint8_t* s = static_cast<uint8_t*>(p);
         std::lock_guard<std::mutex> lk(pool_mu);
@@ -516,7 +504,7 @@ struct Round {
 }  // namespace
 
 void BwDev::loop() {
-    Guard g(device);
+    DeviceGuard g(device);
     Round inflight;
     int next_meta = 0;
     // Wait for round r's cuts and apply them (final cuts, frontier, tail position).  mu not held.
@@ -527,7 +515,7 @@ void BwDev::loop() {
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t e = hipEventSynchronize(M.done);
         t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (e != hipSuccess) return hip_err(e, "writer round");
+        if (e != hipSuccess) return hip_error(e, "writer round");
         float gms = 0, kms = 0, a = 0, z = 0;
         if (hipEventElapsedTime(&gms, M.g0, M.gathered) == hipSuccess) {
             t_gather += gms * 1e-3;
@@ -702,7 +690,7 @@ void BwDev::loop() {
         int rc = overflow ? set_error(KCDC_EIO, "writer arena overflow") : KCDC_OK;
         if (rc == KCDC_OK && ids.on && !compact.empty()) {  // the ring copies may still read these arenas
             hipError_t e = hipStreamWaitEvent(copy, copy_ev, 0);
-            if (e != hipSuccess) rc = hip_err(e, "writer compaction wait");
+            if (e != hipSuccess) rc = hip_error(e, "writer compaction wait");
         }
         // Compactions: one copy launch for all of them (one hipMemcpyAsync each was a blit kernel
         // each), before the gather; their pieces lead the round's piece list.  The ring copies of
@@ -731,7 +719,7 @@ void BwDev::loop() {
             const size_t want = std::max<size_t>(pieces.size() * 2, 1024);
             hipError_t e = hipMalloc(&M.dp, want * sizeof(Piece));
             if (e == hipSuccess) e = hipHostMalloc(&M.hp, want * sizeof(Piece), hipHostMallocDefault);
-            if (e != hipSuccess) rc = hip_err(e, "writer gather list");
+            if (e != hipSuccess) rc = hip_error(e, "writer gather list");
             else M.pcap = want;
         }
         if (rc == KCDC_OK) {
@@ -754,7 +742,7 @@ void BwDev::loop() {
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipEventRecord(M.gathered, copy);
-            if (e != hipSuccess) rc = hip_err(e, "writer gather");
+            if (e != hipSuccess) rc = hip_error(e, "writer gather");
         }
         lap(2);
         // round k's cuts are round k+1's chunk starts
@@ -783,7 +771,7 @@ void BwDev::loop() {
                 const size_t want = std::max<size_t>(words * 2, 1u << 16);
                 hipError_t e = hipMalloc(&M.d, want * 8);
                 if (e == hipSuccess) e = hipHostMalloc(&M.h, want * 8, hipHostMallocDefault);
-                if (e != hipSuccess) rc = hip_err(e, "writer metadata");
+                if (e != hipSuccess) rc = hip_error(e, "writer metadata");
                 else M.cap = want;
             }
             if (rc == KCDC_OK && n) {
@@ -803,7 +791,7 @@ void BwDev::loop() {
                 hipError_t e = hipStreamWaitEvent(stream, M.gathered, 0);
                 if (e == hipSuccess) e = hipEventRecord(M.k0, stream);
                 if (e == hipSuccess) e = hipMemcpyAsync(dp, hp, 5ull * n * 8, hipMemcpyHostToDevice, stream);
-                if (e != hipSuccess) rc = hip_err(e, "writer metadata H2D");
+                if (e != hipSuccess) rc = hip_error(e, "writer metadata H2D");
                 if (rc == KCDC_OK) {
                     SplitArgs s;
                     s.ptrs = reinterpret_cast<const uint8_t* const*>(dp);
@@ -820,11 +808,11 @@ void BwDev::loop() {
                 if (rc == KCDC_OK) {
                     e = hipMemcpyAsync(hp + 5 * n, dp + 5 * n, (n + cuts_cap) * 8, hipMemcpyDeviceToHost, stream);
                     if (e == hipSuccess) e = hipEventRecord(M.done, stream);
-                    if (e != hipSuccess) rc = hip_err(e, "writer cuts D2H");
+                    if (e != hipSuccess) rc = hip_error(e, "writer cuts D2H");
                 }
             } else if (rc == KCDC_OK) {
                 hipError_t e = hipEventRecord(M.done, copy);
-                if (e != hipSuccess) rc = hip_err(e, "writer round event");
+                if (e != hipSuccess) rc = hip_error(e, "writer round event");
             }
         }
         lap(4);
@@ -892,7 +880,7 @@ int BwDev::ids_enable(const char* name, const uint8_t* key, uint32_t key_len) {
     ring_cap = std::max<uint64_t>(64 * round_bytes, 1ull << 30);
     if (test_id_ring_bytes()) ring_cap = std::max<uint64_t>(test_id_ring_bytes(), 16) & ~uint64_t(15);  // tests: wrap and backpressure
     chain_cap = 16384;
-    Guard g(device);
+    DeviceGuard g(device);
     hipError_t e = hipStreamCreateWithFlags(&hstream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&idcopy, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&compacted_ev, hipEventDisableTiming);
@@ -916,7 +904,7 @@ int BwDev::ids_enable(const char* name, const uint8_t* key, uint32_t key_len) {
         if (e == hipSuccess) e = hipEventCreate(&st.t0);
         if (e == hipSuccess) e = hipEventCreate(&st.ev);
     }
-    if (e != hipSuccess) return hip_err(e, "writer content IDs: device memory");
+    if (e != hipSuccess) return hip_error(e, "writer content IDs: device memory");
     ids.on = true;
     hth = std::thread([this] { hash_loop(); });
     return KCDC_OK;
@@ -933,7 +921,7 @@ void BwDev::ids_disable() {
         cv_hash.notify_all();
         hth.join();
     }
-    Guard g(device);
+    DeviceGuard g(device);
     for (hipEvent_t* ev : {&compacted_ev, &copy_ev})
         if (*ev) (void)hipEventDestroy(*ev), *ev = nullptr;
     for (hipEvent_t& ev : pub_ev)
@@ -982,10 +970,10 @@ int BwDev::id_create() {
             b->unref_writers();
         }
     } unref{this};
-    Guard g(device);
+    DeviceGuard g(device);
     {
         const hipError_t e = hipStreamWaitEvent(idcopy, compacted_ev, 0);
-        if (e != hipSuccess) return hip_err(e, "writer content IDs: compaction wait");
+        if (e != hipSuccess) return hip_error(e, "writer content IDs: compaction wait");
     }
     std::vector<Chain> made;
     std::vector<Piece> pcs;  // the made chains' ring copies (to 16-byte aligned ring slots)
@@ -1021,7 +1009,7 @@ int BwDev::id_create() {
         ptasks = 0;
         if (e == hipSuccess) e = hipEventRecord(pub_ev[seq % kPubEv], idcopy);
         if (e == hipSuccess) e = hipEventRecord(copy_ev, idcopy);  // (later compactions wait on it)
-        if (e != hipSuccess) return hip_err(e, "writer content IDs: copy event");
+        if (e != hipSuccess) return hip_error(e, "writer content IDs: copy event");
         {
             std::lock_guard<std::mutex> lk(mu);
             pub_seq = seq + 1;
@@ -1124,12 +1112,12 @@ int BwDev::id_issue(Step& st, bool& issued) {
     // the BLAKE2 kinds read new chains' records, the active list and their digests through
     // host-mapped memory (one launch, no copies); kind 3 hashes whole chunks from the step's list
     hipError_t e = hipEventRecord(st.t0, hstream);
-    if (e != hipSuccess) return hip_err(e, "writer content IDs: chain upload");
+    if (e != hipSuccess) return hip_error(e, "writer content IDs: chain upload");
     int rc = KCDC_OK;
     if (ids.kind == 3) {
         e = hipMemcpyAsync(d_ol, st.h_ol, 8ull * n, hipMemcpyHostToDevice, hstream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_ol + chain_cap, st.h_ol + chain_cap, 8ull * n, hipMemcpyHostToDevice, hstream);
-        if (e != hipSuccess) return hip_err(e, "writer content IDs: chunk list");
+        if (e != hipSuccess) return hip_error(e, "writer content IDs: chunk list");
         rc = kcdc_hash_chunks_device(ids.name.c_str(), ring, d_ol, d_ol + chain_cap, nullptr, n, ids.key.data(),
                                      static_cast<uint32_t>(ids.key.size()), d_dig, 32, hstream);
         if (rc == KCDC_OK) e = hipMemcpyAsync(st.h_dig, d_dig, 32ull * n, hipMemcpyDeviceToHost, hstream);
@@ -1139,7 +1127,7 @@ int BwDev::id_issue(Step& st, bool& issued) {
     }
     if (rc != KCDC_OK) return rc;
     if (e == hipSuccess) e = hipEventRecord(st.ev, hstream);
-    if (e != hipSuccess) return hip_err(e, "writer content IDs: hash step");
+    if (e != hipSuccess) return hip_error(e, "writer content IDs: hash step");
     issued = true;
     return KCDC_OK;
 }
@@ -1150,7 +1138,7 @@ int BwDev::id_deliver(Step& st) {
     // round thread's HIP calls (its round waits doubled and the device idled half the time)
     hipError_t q;
     while ((q = hipEventQuery(st.ev)) == hipErrorNotReady) std::this_thread::sleep_for(std::chrono::microseconds(200));
-    if (q != hipSuccess) return hip_err(q, "writer content IDs: hash step");
+    if (q != hipSuccess) return hip_error(q, "writer content IDs: hash step");
     float ms = 0;
     const bool timed = hipEventElapsedTime(&ms, st.t0, st.ev) == hipSuccess;
     std::lock_guard<std::mutex> lk(mu);
@@ -1190,7 +1178,7 @@ int BwDev::id_deliver(Step& st) {
 // The hash thread: keep two steps in flight while chains have blocks left; end once the round
 // thread has stopped and every chain is named (or on an error).
 void BwDev::hash_loop() {
-    Guard g(device);
+    DeviceGuard g(device);
     std::deque<int> live;  // steps in flight, in issue order
     int next = 0;
     for (;;) {
@@ -1260,7 +1248,7 @@ BwDev* dev_new(const Algo* a, int device, int index, uint64_t round_bytes, uint3
     b->arena_cap = (a->max_size() + kHist + 4 * (b->writer_cap + kBlock) + 4095) & ~uint64_t(4095);
     b->wait = std::chrono::microseconds(max_wait_us ? max_wait_us : 2000);
     if (a->kind == kFixed) return b;
-    Guard g(device);
+    DeviceGuard g(device);
     int err = 0;
     if (!device_tables(device, &err)) {
         delete b;
@@ -1277,7 +1265,7 @@ BwDev* dev_new(const Algo* a, int device, int index, uint64_t round_bytes, uint3
     if (e == hipSuccess) e = hipEventCreate(&b->ev_ref);
     if (e == hipSuccess) e = hipEventRecord(b->ev_ref, b->stream);
     if (e != hipSuccess) {
-        hip_err(e, "writer streams");
+        hip_error(e, "writer streams");
         delete b;
         return nullptr;
     }
@@ -1379,7 +1367,7 @@ extern "C" void kcdc_bw_batcher_free(kcdc_bw_batcher* t) {
             for (kcdc_bw* w : b->open) w->b = nullptr;  // writers not freed: kcdc_bw_free frees their arenas
         }
         if (b->algo->kind != kFixed) {
-            Guard g(b->device);
+            DeviceGuard g(b->device);
             (void)hipStreamSynchronize(b->stream);
             (void)hipStreamSynchronize(b->copy);
         }
@@ -1417,7 +1405,7 @@ extern "C" kcdc_bw* kcdc_bw_open_hint(kcdc_bw_batcher* t, uint64_t size_hint) {
     w->counted = size_hint;
     w->fixed_next = b->algo->kind == kFixed ? b->algo->avg : 0;
     if (b->algo->kind != kFixed) {
-        Guard g(b->device);
+        DeviceGuard g(b->device);
         void *p = nullptr, *q = nullptr;
         {
             std::lock_guard<std::mutex> lk(b->mu);
@@ -1648,7 +1636,7 @@ extern "C" void kcdc_bw_free(kcdc_bw* w) {
         in.release();  // kcdc_bw_batcher_free sets `detached` only after `inside` has drained
         while (!ctl->detached.load()) std::this_thread::sleep_for(std::chrono::microseconds(50));
         if (w->arena) {
-            Guard g(w->device);
+            DeviceGuard g(w->device);
             (void)hipFree(w->arena);
             (void)hipFree(w->spare);
         }
@@ -1676,7 +1664,7 @@ extern "C" void kcdc_bw_free(kcdc_bw* w) {
             // split still touches these arenas
             b->arenas.emplace_back(w->arena, w->spare);
         } else if (w->arena) {
-            Guard g(b->device);
+            DeviceGuard g(b->device);
             (void)hipStreamSynchronize(b->copy);
             (void)hipStreamSynchronize(b->stream);
             if (b->idcopy) (void)hipStreamSynchronize(b->idcopy);  // (after an error: ring copies may read it)
@@ -1684,7 +1672,7 @@ extern "C" void kcdc_bw_free(kcdc_bw* w) {
             (void)hipFree(w->spare);
         }
     } else if (w->arena) {  // its batcher was freed first
-        Guard g(w->device);
+        DeviceGuard g(w->device);
         (void)hipFree(w->arena);
         (void)hipFree(w->spare);
     }

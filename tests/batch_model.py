@@ -21,20 +21,20 @@ Three parts, all numpy on top of tests/long_model.py (slot tables, hashes, candi
 
   geometry    a restatement -- not an import -- of how the kernels tile a chunk's test region
               (kopia_amd/csrc/kcdc_kernels.hip):
-                pregion (l. 1374-1383): lo = s + min - 1 + off0, hi = min(s + max - 1, n - 1) + off0
+                pregion: lo = s + min - 1 + off0, hi = min(s + max - 1, n - 1) + off0
                   in coordinates (off0 = the stream pointer's misalignment, 0..15);
-                pstream_region (l. 816-828): the region's tile 0 starts at lo & ~127;
-                tile_geom (l. 674-684), buzhash: a tile at ct is 64 lanes of
+                pstream_region: the region's tile 0 starts at lo & ~127;
+                tile_geom, buzhash: a tile at ct is 64 lanes of
                   L = min(roundup128(ceil((hi - ct + 1) / 64)), lane_cap) bytes, scanned in 128-byte
-                  steps; a step that begins past hi is skipped (l. 1873, `cl <= hi_rel`);
-                rk_geom (l. 2173-2183), Rabin-Karp: L rounded up to 256 and capped at 2 * lane_cap
-                  (kRkLaneMul, l. 2307, 2328); chain A scans a lane's first half, chain B its
-                  second (rk_dma_warm, l. 2186-2197); checks are per 64 bytes, the last 64 bytes
-                  of B are the drain step (rk_walk, l. 2232-2303);
-                the next tile starts at ct + 64 * L (visit_tile, l. 1562; l. 2447);
-                a help task is one owner tile [ct, min(ct + T - 1, hi)] (help_find, l. 1257-1259)
-                  scanned in sub-tiles with lanes of half the cap (l. 1775, 1810; l. 2445), its
-                  lower clip the task's own ct (pregion, l. 1375-1378).
+                  steps; a step that begins past hi is skipped (split_batch_pipe_kernel, `cl <= hi_rel`);
+                rk_geom, Rabin-Karp: L rounded up to 256 and capped at 2 * lane_cap
+                  (kRkLaneMul); chain A scans a lane's first half, chain B its
+                  second (rk_dma_warm); checks are per 64 bytes, the last 64 bytes
+                  of B are the drain step (rk_walk);
+                the next tile starts at ct + 64 * L (visit_tile; split_batch_rk_kernel);
+                a help task is one owner tile [ct, min(ct + T - 1, hi)] (help_find)
+                  scanned in sub-tiles with lanes of half the cap (both batch kernels), its
+                  lower clip the task's own ct (pregion).
               tests/test_gpu_batch_edges.py checks the lane cap assumed here against the
               library's batch_plan (kcdc_test_batch_plan) before it trusts a layout.
 """
