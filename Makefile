@@ -5,11 +5,11 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 CSRC := kopia_amd/csrc
 OBJ := build/obj
-SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
+SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 LIB := kopia_amd/libkcdc.so
 
-all: $(LIB) oracle build/writer_bench
+all: $(LIB) oracle build/writer_bench build/s2_decode_host
 
 # every object depends on every header of the sources' directory: a header edit rebuilds
 HDRS := $(wildcard $(CSRC)/*.h) include/kcdc.h
@@ -41,7 +41,7 @@ clean:
 build/libkcdc_dbg.so build/libkcdc_trace.so: $(SRCS) $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(if $(findstring dbg,$@),-DKCDC_DEBUG_CHECKS=1,-DKCDC_TRACE=1) -shared -o $@ \
-	  $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip \
+	  $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_ecc.hip \
 	  -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
 instrumented: build/libkcdc_dbg.so build/libkcdc_trace.so
 .PHONY: instrumented
@@ -62,7 +62,7 @@ variants:
 	@for v in $(VARIANTS); do \
 	  n=$${v%%:*}; f=$$(echo $${v#*:} | tr ',' ' '); \
 	  echo "variant $$n: $$f"; \
-	  $(HIPCC) $(HIPFLAGS) $$f -shared -o build/variants/libkcdc_$$n.so $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_ecc.hip -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp || exit 1; \
+	  $(HIPCC) $(HIPFLAGS) $$f -shared -o build/variants/libkcdc_$$n.so $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_ecc.hip -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp || exit 1; \
 	done
 .PHONY: variants
 
@@ -70,6 +70,12 @@ variants:
 build/writer_bench: tools/writer_bench.cpp include/kcdc.h $(LIB)
 	@mkdir -p build
 	g++ -O2 -std=c++17 -pthread -Iinclude $< -Lkopia_amd -lkcdc -Wl,-rpath,'$$ORIGIN/../kopia_amd' -o $@
+
+# The S2 decoder's validity header on the CPU under the host sanitizers (tests/test_s2_vectors.py
+# runs every vector through it before the GPU sees one)
+build/s2_decode_host: tools/s2_decode_host.cpp $(CSRC)/kcdc_s2_format.h $(CSRC)/kcdc_wave.h
+	@mkdir -p build
+	g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan -I$(CSRC) $< -o $@
 
 # Microbenchmarks run by tools/gpu_session.sh (valu:, membench): standalone HIP programs
 build/valu_rate: tools/valu_rate.hip

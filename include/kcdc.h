@@ -392,6 +392,44 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
                                 const uint64_t* d_out_offsets, uint64_t* d_out_lens, uint32_t* d_header_ids,
                                 void* d_work, uint64_t work_bytes, void* hip_stream);
 
+/* ------------------------------------------------------------- content decompression
+ * The read path's counterpart for many contents per call: what the committed read manager does
+ * with every content whose index entry carries a compression header ID
+ * (c.Decompress(output, tmp.Bytes().Reader(), true), repo/content/committed_read_manager.go:336),
+ * for the s2-* compressors (s2Compressor.Decompress, compressor_s2.go:73-90: verifyCompressionHeader,
+ * compressor.go:107-119, then s2.NewReader over the rest):
+ *   content_i = BE32(header ID) || S2 stream      exactly what kcdc_compress_chunks_device writes
+ * The stream is anything s2.NewReader accepts: the Snappy framing format (stream identifier
+ * "S2sTwO" or "sNaPpY", compressed and uncompressed data chunks with the masked CRC-32C of their
+ * decoded bytes, padding and skippable chunks), blocks of up to 4 MiB made of Snappy's literal,
+ * copy-1, copy-2 and copy-4 elements, and S2's repeat offsets.  Every CRC is checked.
+ * kcdc_decompression_algorithms: the names decoded on the device (the four s2-*).
+ * kcdc_decompress_workspace_size: device scratch for nchunks contents whose output slots hold
+ *   total_out_cap_bytes in all: one 32-byte block descriptor per content and one per 16 KiB of
+ *   slot, plus 24 bytes per content and fixed fields.  Content i may have 1 + d_out_caps[i] / 16 KiB
+ *   data chunks (writers emit blocks of 32 KiB, 64 KiB or 1 MiB), plus an equal share of whatever
+ *   descriptor room a larger work_bytes gives beyond that.
+ * kcdc_decompress_chunks_device: content i = [d_offsets[i], +d_comp_lens[i]) of d_comp (any
+ *   alignment); its bytes go to d_out + d_out_offsets[i] (any alignment), at most d_out_caps[i] of
+ *   them (the caller knows the original length from the index).  d_status[i]: 0 with
+ *   d_out_lens[i] the decoded length; KCDC_EBADMSG if the first four bytes are not this name's
+ *   header ID ("invalid compression header"), the framing or a block is malformed, or a CRC-32C
+ *   does not match; KCDC_EOVERFLOW if the decoded length would exceed the cap; KCDC_ENOMEM if the
+ *   content has more data chunks than d_work has room for.  On a failure d_out_lens[i] = 0 and
+ *   the slot's contents are unspecified; no byte outside [d_out_offsets[i], +d_out_caps[i]) is
+ *   written, the content's compressed bytes are read through aligned 4-byte words that hold at least
+ *   one of them, and no other content of the call is affected.  d_work: 8-byte aligned.
+ *   Returns KCDC_ENOENT for an unknown name, KCDC_EINVAL for a registered compressor with no
+ *   device decoder (deflate-*, gzip*, pgzip*, zstd*).  Asynchronous on hip_stream: no host
+ *   synchronisation and no copy to the host; d_work must stay allocated until the work finishes. */
+int kcdc_decompression_algorithms(const char** names, int cap);
+uint64_t kcdc_decompress_workspace_size(uint64_t total_compressed_bytes, uint64_t total_out_cap_bytes,
+                                        uint32_t nchunks);
+int kcdc_decompress_chunks_device(const char* algorithm, const uint8_t* d_comp, const uint64_t* d_offsets,
+                                  const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
+                                  const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_lens,
+                                  int32_t* d_status, void* d_work, uint64_t work_bytes, void* hip_stream);
+
 /* ------------------------------------------------------------- error correction
  * Kopia's ECC layer for many chunks per call: repo/ecc, REED-SOLOMON-CRC32 (ecc_rs_crc.go).  A
  * repository created with an ECC overhead wraps its encryptor in encryptorWrapper

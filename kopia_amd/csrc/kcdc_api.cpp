@@ -1023,3 +1023,35 @@ extern "C" int kcdc_ecc_matrix(int32_t data_shards, int32_t parity_shards, uint8
     if (data_shards < 1 || parity_shards < 1) return set_error(KCDC_EINVAL, "coding matrix: shard counts must be positive");
     return ecc_matrix(static_cast<uint32_t>(data_shards), static_cast<uint32_t>(parity_shards), out);
 }
+
+// ======================================================= content decompression
+extern "C" int kcdc_decompression_algorithms(const char** names, int cap) { return comp_s2_names(names, cap); }
+
+extern "C" uint64_t kcdc_decompress_workspace_size(uint64_t total_compressed_bytes, uint64_t total_out_cap_bytes,
+                                                   uint32_t nchunks) {
+    (void)total_compressed_bytes;  // descriptors are counted by output: a block decodes to at most 4 MiB
+    return decompress_workspace_size(total_out_cap_bytes, nchunks);
+}
+
+extern "C" int kcdc_decompress_chunks_device(const char* algorithm, const uint8_t* d_comp, const uint64_t* d_offsets,
+                                             const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
+                                             const uint64_t* d_out_offsets, const uint64_t* d_out_caps,
+                                             uint64_t* d_out_lens, int32_t* d_status, void* d_work,
+                                             uint64_t work_bytes, void* hip_stream) {
+    uint32_t header_id = 0;
+    bool s2 = false;
+    if (comp_lookup(algorithm, &header_id, &s2) != 0)
+        return set_error(KCDC_ENOENT, std::string("unknown compression algorithm: ") + (algorithm ? algorithm : "(null)"));
+    if (!s2)
+        return set_error(KCDC_EINVAL, std::string("no device decoder for compression algorithm ") + algorithm +
+                                          " (the s2-* streams are decoded on the device)");
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (int rc = check_device(dev)) return rc;
+    if (nchunks == 0) return KCDC_OK;
+    if (!d_comp || !d_offsets || !d_comp_lens || !d_out || !d_out_offsets || !d_out_caps || !d_out_lens || !d_status ||
+        !d_work)
+        return set_error(KCDC_EINVAL, "null argument");
+    return launch_decompress(header_id, d_comp, d_offsets, d_comp_lens, nchunks, d_out, d_out_offsets, d_out_caps,
+                             d_out_lens, d_status, d_work, work_bytes, hip_stream);
+}

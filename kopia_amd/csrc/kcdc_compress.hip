@@ -42,6 +42,7 @@
 #include <string>
 
 #include "kcdc_internal.h"
+#include "kcdc_wave.h"
 
 namespace kcdc {
 namespace compdev {
@@ -2385,16 +2386,7 @@ __global__ __launch_bounds__(1024) void span_pos_kernel(CompArgs a) {
 // 512 bytes per lane; lanes combine in a 6-level tree with the constants x^(2^(12+j)), the span
 // is scaled by x^(8 * 32768 * spans after it), and the chunk's word takes the XOR (atomic, order
 // free).  The frame kernel adds crc32 of len zero bytes (the init / final-XOR terms).
-constexpr uint32_t kCrcPoly = 0xEDB88320u;   // CRC-32 (gzip), reflected
-constexpr uint32_t kCrc32cPoly = 0x82F63B78u; // CRC-32C (Castagnoli: the S2 / Snappy framing), reflected
-__host__ __device__ __forceinline__ uint32_t multmodp(uint32_t a, uint32_t b, uint32_t poly = kCrcPoly) {
-    uint32_t p = 0;  // a * b mod P (reflected)
-    for (int i = 31; i >= 0; i--) {
-        p ^= ((a >> i) & 1u) ? b : 0u;
-        b = (b >> 1) ^ (poly & (0u - (b & 1u)));
-    }
-    return p;
-}
+// multmodp, the polynomials, the LDS byte table and wave_copy: kcdc_wave.h (shared with the decoder)
 
 // S2 = false: gzip's CRC-32 of each chunk, its 32 KiB spans counted back from the chunk's end.
 // S2 = true: the CRC-32C of each S2 span on its own (a framing chunk's checksum), lanes counted
@@ -2404,11 +2396,7 @@ template <bool S2>
 __global__ __launch_bounds__(64 * kCrcWaves) void crc_spans_kernel(CompArgs a) {
     constexpr uint32_t poly = S2 ? kCrc32cPoly : kCrcPoly;
     __shared__ uint32_t tab[256 * 32];  // 32 copies: lane l reads copy l & 31 (conflict free)
-    for (uint32_t x = threadIdx.x; x < 256u; x += 64u * kCrcWaves) {
-        uint32_t r = x;
-        for (int k = 0; k < 8; k++) r = (r >> 1) ^ (poly & (0u - (r & 1u)));
-        for (uint32_t c = 0; c < 32u; c++) tab[32u * x + ((c + x) & 31u)] = r;
-    }
+    crc_table_fill(tab, poly, 64u * kCrcWaves);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t b = blockIdx.x * kCrcWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2487,40 +2475,6 @@ __global__ __launch_bounds__(64 * kCrcWaves) void crc_spans_kernel(CompArgs a) {
             if (after & 1u) r = multmodp(r, a.x2n[18 + bit]);
         atomicXor(&a.crc[c], r);
     }
-}
-
-// n bytes from src to dst, both at any alignment, by one wave: byte stores for dst's partial
-// head and tail words, aligned dword stores (from two aligned loads + alignbit) in between.
-// Only aligned source words holding a byte of [src, src + n) are read.
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
-    const uint32_t head = min(n, static_cast<uint32_t>((4u - (reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u));
-    if (lane < head) dst[lane] = src[lane];
-    const uint32_t m = (n - head) >> 2;
-    uint32_t* __restrict__ dw = reinterpret_cast<uint32_t*>(dst + head);
-    const uint8_t* s0 = src + head;
-    const uint32_t sh = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(s0) & 3u);
-    const uint32_t* __restrict__ sw = reinterpret_cast<const uint32_t*>(s0 - sh);
-    // 8 words per lane in flight per round (loads first, then stores): one dependent load per
-    // 256 bytes left a copy latency-bound at the emit kernel's two waves per CU
-    constexpr uint32_t kU = 8;
-    uint32_t i = lane;
-    for (; i + 64u * (kU - 1u) < m; i += 64u * kU) {
-        uint32_t w0[kU], w1[kU];
-#pragma unroll
-        for (uint32_t u = 0; u < kU; u++) {
-            w0[u] = sw[i + 64u * u];
-            w1[u] = sh ? sw[i + 64u * u + 1u] : 0u;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < kU; u++) dw[i + 64u * u] = __builtin_amdgcn_alignbit(w1[u], w0[u], 8u * sh);
-    }
-    for (; i < m; i += 64u) {
-        const uint32_t w0 = sw[i];
-        const uint32_t w1 = sh ? sw[i + 1] : 0u;
-        dw[i] = __builtin_amdgcn_alignbit(w1, w0, 8u * sh);
-    }
-    const uint32_t done = head + 4u * m;
-    if (lane < n - done) dst[done + lane] = src[done + lane];
 }
 
 // Zstandard frame header of a chunk of `len` bytes (RFC 8878 §3.1.1.1): magic, Frame_Header_Descriptor
@@ -2864,6 +2818,22 @@ CompWs comp_ws(uint32_t n, uint64_t max_spans) {
 using namespace kcdc;
 
 namespace kcdc {
+int comp_lookup(const char* name, uint32_t* header_id, bool* s2) {
+    const CompAlgo* a = find_comp(name);
+    if (!a) return -2;
+    *header_id = a->header_id;
+    *s2 = a->fmt == compdev::kFmtS2;
+    return 0;
+}
+int comp_s2_names(const char** names, int cap) {
+    int n = 0;
+    for (const CompAlgo& a : kCompAlgos)
+        if (a.fmt == compdev::kFmtS2) {
+            if (names && n < cap) names[n] = a.name;
+            n++;
+        }
+    return n;
+}
 int test_set_deflate_limit(bool cl, int64_t value) {
     if (value != 0 && (value < (cl ? 5 : 9) || value > (cl ? 7 : 15)))
         return set_error(-22, cl ? "deflate code-length code limit: 0 (default 7), or bits in [5, 7]"
@@ -2935,15 +2905,8 @@ extern "C" int kcdc_compress_chunks_device(const char* name, const uint8_t* d_da
     a.maxb_cl = g_test_maxb_cl ? g_test_maxb_cl : 7u;
     a.crc = reinterpret_cast<uint32_t*>(w + l.crc);
     a.span_crc = reinterpret_cast<uint32_t*>(w + l.span_crc);
-    {
-        uint32_t p = 1u << 30, q = 1u << 30;  // x^1
-        for (int k = 0; k < 32; k++) {
-            a.x2n[k] = p;
-            a.x2nc[k] = q;
-            p = compdev::multmodp(p, p);
-            q = compdev::multmodp(q, q, compdev::kCrc32cPoly);
-        }
-    }
+    compdev::crc_x2n_table(compdev::kCrcPoly, a.x2n);
+    compdev::crc_x2n_table(compdev::kCrc32cPoly, a.x2nc);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(compdev::span_count_kernel, dim3((nchunks + 255u) / 256u), dim3(256), 0, st, a);
     hipLaunchKernelGGL(compdev::span_scan_kernel, dim3(1), dim3(1024), 0, st, nchunks, a.spans);

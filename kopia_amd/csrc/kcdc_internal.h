@@ -126,6 +126,15 @@ int launch_hash_chains(const char* name, const uint8_t* key, uint32_t key_len, H
                        const HashChain* fresh, const uint32_t* d_active, uint32_t nactive, uint64_t max_blocks,
                        uint8_t* d_digests, uint32_t digest_stride, void* stream);
 
+// ---- content decompression (kcdc_decompress.hip); the compressor registry is kcdc_compress.hip's
+// 0 with the name's header ID and whether its stream is S2 framing, or -2 for an unregistered name.
+int comp_lookup(const char* name, uint32_t* header_id, bool* s2);
+int comp_s2_names(const char** names, int cap);  // the s2-* names (sorted); returns their count
+uint64_t decompress_workspace_size(uint64_t total_out_cap_bytes, uint32_t nchunks);
+int launch_decompress(uint32_t header_id, const uint8_t* d_comp, const uint64_t* d_offsets, const uint64_t* d_comp_lens,
+                      uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets, const uint64_t* d_out_caps,
+                      uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
+
 // ---- error correction (repo/ecc): parameters and geometry, shared by the host code and kcdc_ecc.hip
 #if defined(__HIPCC__)
 #define KCDC_HD __host__ __device__
