@@ -41,8 +41,7 @@ clean:
 build/libkcdc_dbg.so build/libkcdc_trace.so: $(SRCS) $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(if $(findstring dbg,$@),-DKCDC_DEBUG_CHECKS=1,-DKCDC_TRACE=1) -shared -o $@ \
-	  $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_ecc.hip \
-	  -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
+	  $(filter %.hip,$(SRCS)) -x hip $(filter %.cpp,$(SRCS))
 instrumented: build/libkcdc_dbg.so build/libkcdc_trace.so
 .PHONY: instrumented
 
@@ -62,7 +61,7 @@ variants:
 	@for v in $(VARIANTS); do \
 	  n=$${v%%:*}; f=$$(echo $${v#*:} | tr ',' ' '); \
 	  echo "variant $$n: $$f"; \
-	  $(HIPCC) $(HIPFLAGS) $$f -shared -o build/variants/libkcdc_$$n.so $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_ecc.hip -x hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp || exit 1; \
+	  $(HIPCC) $(HIPFLAGS) $$f -shared -o build/variants/libkcdc_$$n.so $(filter %.hip,$(SRCS)) -x hip $(filter %.cpp,$(SRCS)) || exit 1; \
 	done
 .PHONY: variants
 

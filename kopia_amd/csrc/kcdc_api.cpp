@@ -1,6 +1,6 @@
 // C ABI of libkcdc (include/kcdc.h): the drop-in boundary for Kopia's
 // repo/splitter package.  Host orchestration only; every byte of hashing runs
-// in the gfx950 kernels of kcdc_kernels.hip.  There is no CPU fallback.
+// in the gfx950 kernels of kcdc_kernels.hip (kcdc_split_*.h).  There is no CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

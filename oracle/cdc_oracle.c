@@ -256,7 +256,7 @@ void orc_gorand_read(int64_t seed, const uint64_t* cooked, uint8_t* out, int64_t
 /* ------------------------------------------------- counter PRNG stream data
  * Synthetic stream bytes for configs 2-5 (BASELINE.json): 64-bit word j of
  * stream `sid` = mix64(key + (j+1)*golden), key = mix64(seed ^ mix64(sid + c)).
- * The GPU generator in kopia_amd/csrc/kcdc_kernels.hip computes the same words. */
+ * The GPU generator in kopia_amd/csrc/kcdc_split_scan.h computes the same words. */
 static inline uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

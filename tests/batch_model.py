@@ -20,7 +20,7 @@ Three parts, all numpy on top of tests/long_model.py (slot tables, hashes, candi
               it asserts from the model that the stream's candidates are exactly the planted ones.
 
   geometry    a restatement -- not an import -- of how the kernels tile a chunk's test region
-              (kopia_amd/csrc/kcdc_kernels.hip):
+              (kopia_amd/csrc/kcdc_split_queue.h, _feed.h, _visit.h, _buz.h, _rk.h):
                 pregion: lo = s + min - 1 + off0, hi = min(s + max - 1, n - 1) + off0
                   in coordinates (off0 = the stream pointer's misalignment, 0..15);
                 pstream_region: the region's tile 0 starts at lo & ~127;

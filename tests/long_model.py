@@ -6,7 +6,7 @@ the product imports it.
 The long path scans every 128 KiB *coordinate* segment of a stream for candidates (positions
 whose window hash has its masked bits zero), keeps the first kSegK = 8 of each segment, and
 resolves the chunk rule over that list, rescanning where a truncated segment may hide the
-candidate it needs (kopia_amd/csrc/kcdc_kernels.hip, "long single stream").  Which of those
+candidate it needs (kopia_amd/csrc/kcdc_split_long.h, "long single stream").  Which of those
 branches an input reaches depends only on where its candidates lie, so this module computes
 exactly that, in numpy, from the hashes' definitions and not from the kernels:
 

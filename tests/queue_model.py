@@ -3,7 +3,7 @@
 Test infrastructure only (tests/test_queue_model.py): nothing in the product imports it.
 
 It restates, wave by wave, the state machine that `split_batch_pipe_kernel` (buzhash) and
-`split_batch_rk_kernel` (Rabin-Karp) in kopia_amd/csrc/kcdc_kernels.hip run over the shared
+`split_batch_rk_kernel` (Rabin-Karp) in kopia_amd/csrc (kcdc_split_buz.h, kcdc_split_rk.h) run over the shared
 queue and help memory, at the granularity at which other waves can observe it: every global
 memory operation (the {head, tail} ticket atomic, ring-entry writes and reads, the done counter,
 the workgroup flags, the help slots' claim words, granules, result rows, bitmap and held-ticket
@@ -115,7 +115,7 @@ def make_streams(rng, n, max_regions, max_tiles):
 
 @dataclass
 class PStream:
-    """The wave's `cur` (kcdc_kernels.hip struct PStream): an own stream or a help task."""
+    """The wave's `cur` (kcdc_split_queue.h struct PStream): an own stream or a help task."""
     sid: int
     help: bool = False
     r: int = 0                       # own: region index (s)
@@ -185,7 +185,7 @@ class Launch:
         cur.cnt += 1
 
     def pstream_region(self, cur):
-        """Set up the next region (kcdc_kernels.hip pstream_region); False when finished."""
+        """Set up the next region (kcdc_split_queue.h pstream_region); False when finished."""
         if cur.ti is not None:
             return True
         regs = self.st[cur.sid].regions

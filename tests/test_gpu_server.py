@@ -1,5 +1,5 @@
 """GPU: the resident scan server behind private streaming handles (kcdc_splitter_next ->
-server_scan_first, kcdc_kernels.hip scan_server_kernel).  Cuts must be identical with the
+server_scan_first in kcdc_kernels.hip, scan_server_kernel in kcdc_split_scan.h).  Cuts must be identical with the
 server on and off and equal the oracle's, across the server's idle exit and relaunch, scratch
 growth to whole-chunk slices, and concurrent handles (the busy server falls back to a launch).
 test_wave_seams plants candidates on the seams between the eight waves' sub-ranges of a

@@ -48,7 +48,7 @@ def test_help_windows_keep_the_invariants(kind, window):
 
 
 def test_budget_help_mutation_is_caught():
-    """Round 5's orphaned ring entries: budget_out without !is_help (kcdc_kernels.hip budget_out in
+    """Round 5's orphaned ring entries: budget_out without !is_help (kcdc_split_visit.h / kcdc_split_rk.h budget_out in
     split_batch_pipe_kernel) reserves entries a help tile never writes."""
     bad = [s for s in range(100) if qm.random_launch(s, "buz" if s % 2 else "rk", (qm.MUT_BUDGET_HELP,)).check()]
     assert len(bad) >= 5, bad

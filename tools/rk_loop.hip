@@ -1,6 +1,6 @@
 // Rabin-Karp hot-loop variants in isolation (round 6): what bounds split_batch_rk_kernel's
 // per-byte chain, measured rather than argued.  Each variant is a replica of rk_step64
-// (kcdc_kernels.hip) fed from an LDS step slot, no DMA, queue, warm-up or tile overhead, over
+// (kcdc_split_rk.h) fed from an LDS step slot, no DMA, queue, warm-up or tile overhead, over
 // config 2's rolled bytes (6.7429e9 B under 4M-RABINKARP), one workgroup per CU.
 //
 //   NCH     chains per lane (2: production; 4: the lane segment in quarters)

@@ -22,8 +22,8 @@ sys.path.insert(0, ROOT)
 from oracle import coracle  # noqa: E402  (test/measurement infrastructure only)
 
 WAVE, SEED = 64, 0x6B6F706961
-LANE_MAX = int(os.environ.get("KCDC_LANE_MAX", "2048"))  # kcdc_kernels.hip kLaneMax
-TILE_DIV = int(os.environ.get("KCDC_TILE_DIV", "256"))  # kcdc_kernels.hip kTileDiv
+LANE_MAX = int(os.environ.get("KCDC_LANE_MAX", "2048"))  # kcdc_split_base.h kLaneMax
+TILE_DIV = int(os.environ.get("KCDC_TILE_DIV", "256"))  # kcdc_split_base.h kTileDiv
 
 
 def lane_cap(avg):

@@ -103,7 +103,7 @@ int run_all(int cus, uint32_t* out, uint64_t* cyc, std::integer_sequence<int, K.
 }
 
 // The Rabin-Karp batch kernel's hot loop in isolation (a replica of rk_step64 in
-// kcdc_kernels.hip: two chains per lane interleaved byte by byte, 16 mod[] replicas and 32 out[]
+// kcdc_split_rk.h: two chains per lane interleaved byte by byte, 16 mod[] replicas and 32 out[]
 // replicas in LDS, bit-reversed state, the running v_min3 test, outx[] reads two bytes ahead),
 // fed from an LDS step slot (8 ds_read_b128 + 32 v_bfrev per 128 bytes, as the kernel's
 // rk_read_step128) instead of the DMA ring, at the kernel's occupancy (one 512-thread workgroup
