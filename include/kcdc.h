@@ -421,7 +421,8 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
  *   one of them, and no other content of the call is affected.  d_work: 8-byte aligned.
  *   Returns KCDC_ENOENT for an unknown name, KCDC_EINVAL for a registered compressor with no
  *   device decoder (deflate-*, gzip*, pgzip*, zstd*).  Asynchronous on hip_stream: no host
- *   synchronisation and no copy to the host; d_work must stay allocated until the work finishes. */
+ *   synchronisation and no copy to the host; d_work must stay allocated until the work finishes.
+ *   The deflate-*, gzip* and pgzip* names are decoded by the kcdc_inflate_* family below. */
 int kcdc_decompression_algorithms(const char** names, int cap);
 uint64_t kcdc_decompress_workspace_size(uint64_t total_compressed_bytes, uint64_t total_out_cap_bytes,
                                         uint32_t nchunks);
@@ -429,6 +430,44 @@ int kcdc_decompress_chunks_device(const char* algorithm, const uint8_t* d_comp, 
                                   const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
                                   const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_lens,
                                   int32_t* d_status, void* d_work, uint64_t work_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------- inflate
+ * The same step of the read path (c.Decompress, repo/content/committed_read_manager.go:336) for the
+ * nine compressors whose stream is RFC 1951: deflateCompressor.Decompress
+ * (compressor_deflate.go:64-78: verifyCompressionHeader, then flate.NewReader),
+ * gzipCompressor.Decompress (compressor_gzip.go:68-85: gzip.NewReader) and pgzipCompressor.Decompress
+ * (compressor_pgzip.go: pgzip.NewReader):
+ *   content_i = BE32(header ID) || raw deflate stream                 deflate-*
+ *   content_i = BE32(header ID) || RFC 1952 member(s)                  gzip*, pgzip*
+ * from any writer, not only kcdc_compress_chunks_device.  A raw stream is stored, fixed and dynamic
+ * blocks in any order and number, distances up to 32768 reaching back across blocks to the first
+ * output byte; whatever follows its final block is ignored, as the Go reader leaves it unread.  A
+ * member is 1f 8b 08, FLG with FEXTRA, FNAME, FCOMMENT and FHCRC honoured (the header CRC-16 is
+ * checked), the stream, CRC-32 and ISIZE (both checked); further members may follow, as with Go's
+ * multistream reader, and their output is appended; anything after a trailer that is not a whole
+ * valid member is an error.  The choices made where zlib and Go's readers differ are listed in
+ * kopia_amd/csrc/kcdc_inflate_format.h.
+ * kcdc_inflate_algorithms: the nine names, sorted.
+ * kcdc_inflate_workspace_size: device scratch for nchunks contents: a ticket and 32 bytes per
+ *   content, whatever their sizes (a bit stream has no block index to make room for).
+ * kcdc_inflate_chunks_device: the arguments and the contract of kcdc_decompress_chunks_device.
+ *   d_status[i]: 0 with d_out_lens[i] the decoded length; KCDC_EBADMSG for a wrong header ID, a
+ *   malformed stream or member, a CRC-32 or ISIZE mismatch, or truncation; KCDC_EOVERFLOW if the
+ *   decoded bytes would exceed d_out_caps[i].  On a failure d_out_lens[i] = 0 and the slot's
+ *   contents are unspecified; no byte outside the slot is written, compressed bytes are read through
+ *   aligned 4-byte words that hold at least one byte of the content, and no other content of the
+ *   call is affected.  Positions are 32 bits on the device: a content of 4 GiB or more gets
+ *   KCDC_EBADMSG, and a cap above 4 GiB - 1 counts as 4 GiB - 1.  d_work: 8-byte aligned.
+ *   Returns KCDC_ENOENT for an unknown name and
+ *   KCDC_EINVAL for a registered name of another format (s2-*, zstd*).  nchunks == 0 launches
+ *   nothing.  Asynchronous on hip_stream: no host synchronisation and no copy to the host; d_work
+ *   must stay allocated until the work finishes. */
+int kcdc_inflate_algorithms(const char** names, int cap);
+uint64_t kcdc_inflate_workspace_size(uint32_t nchunks);
+int kcdc_inflate_chunks_device(const char* algorithm, const uint8_t* d_comp, const uint64_t* d_offsets,
+                               const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
+                               const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_lens,
+                               int32_t* d_status, void* d_work, uint64_t work_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------- error correction
  * Kopia's ECC layer for many chunks per call: repo/ecc, REED-SOLOMON-CRC32 (ecc_rs_crc.go).  A

@@ -135,6 +135,10 @@ _SIGS = {
     "kcdc_decompress_workspace_size": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "kcdc_decompress_chunks_device": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
                                                 _P]),
+    "kcdc_inflate_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),
+    "kcdc_inflate_workspace_size": (C.c_uint64, [C.c_uint32]),
+    "kcdc_inflate_chunks_device": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                             _P]),
     "kcdc_ecc_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),
     "kcdc_ecc_default_algorithm": (C.c_char_p, []),
     "kcdc_ecc_params": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(EccInfo)]),

@@ -4,7 +4,9 @@ mirroring Kopia's compression package for the deflate, gzip, pgzip and s2 compre
 compressor_gzip.go, compressor_pgzip.go, compressor_s2.go; compression_ids.go) and the content manager's keep-or-drop rule
 (repo/content/content_manager_lock_free.go:42-73: the compressed form is kept only when it is
 shorter than the content, else the header ID is NoCompression = 0).  The read path's Decompress
-(compressor_s2.go:73-90, called by committed_read_manager.go:336) runs on the device for the s2 names.
+(called by committed_read_manager.go:336) runs on the device for the s2 names
+(compressor_s2.go:73-90: decompress_chunks_device) and for the deflate, gzip and pgzip names
+(compressor_deflate.go:64-78, compressor_gzip.go:68-85, compressor_pgzip.go: inflate_chunks_device).
 No CPU fallback for the byte path: the library must be loaded."""
 from __future__ import annotations
 
@@ -28,6 +30,13 @@ def DecompressibleAlgorithms() -> list[str]:
     """The names whose streams decompress_chunks_device decodes (the s2 compressors)."""
     arr = (C.c_char_p * 64)()
     n = _lib.lib().kcdc_decompression_algorithms(arr, 64)
+    return [arr[i].decode() for i in range(n)]
+
+
+def InflatableAlgorithms() -> list[str]:
+    """The names whose streams inflate_chunks_device decodes (deflate-*, gzip*, pgzip*)."""
+    arr = (C.c_char_p * 64)()
+    n = _lib.lib().kcdc_inflate_algorithms(arr, 64)
     return [arr[i].decode() for i in range(n)]
 
 
@@ -115,6 +124,34 @@ class Compressor:
             wb = int(_lib.lib().kcdc_decompress_workspace_size(int(lens.sum()), int(caps.sum()), n))
             work = torch.empty(max(wb, 8), dtype=torch.uint8, device=device)
         _lib.check(_lib.lib().kcdc_decompress_chunks_device(
+            self.name.encode(), C.c_void_p(comp_ptr), d_offs.data_ptr(), d_lens.data_ptr(), n, d_out.data_ptr(),
+            d_oo.data_ptr(), d_caps.data_ptr(), out_lens.data_ptr(), status.data_ptr(), work.data_ptr(), wb,
+            C.c_void_p(stream.cuda_stream)))
+        out_lens._kcdc_keep = (d_offs, d_lens, d_oo, d_caps, work)  # alive until the caller syncs
+        return out_lens[:n], status[:n]
+
+    def inflate_chunks_device(self, comp_ptr: int, offsets, lengths, d_out, out_offsets, out_caps, device, stream=None):
+        """decompress_chunks_device for the deflate-*, gzip* and pgzip* names: content i =
+        [offsets[i], +lengths[i]) of the device bytes at comp_ptr (the 4-byte header ID, then a raw
+        deflate stream or gzip members, from any writer) into d_out at out_offsets[i], at most
+        out_caps[i] bytes.  Returns device tensors (out_lens int64, status int32): status[i] is 0
+        with out_lens[i] the decoded length, or KCDC_EBADMSG (wrong header ID, malformed or
+        truncated stream or member, CRC-32 or ISIZE mismatch) or KCDC_EOVERFLOW (longer than the
+        cap) with out_lens[i] = 0.  Asynchronous on `stream`."""
+        import torch
+        n = len(offsets)
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        with torch.cuda.stream(stream):
+            out_lens = torch.empty(max(n, 1), dtype=torch.int64, device=device)
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+            d_offs = torch.as_tensor(np.asarray(offsets, dtype=np.int64)).to(device)
+            d_lens = torch.as_tensor(np.asarray(lengths, dtype=np.int64)).to(device)
+            d_oo = torch.as_tensor(np.asarray(out_offsets, dtype=np.int64)).to(device)
+            d_caps = torch.as_tensor(np.asarray(out_caps, dtype=np.int64)).to(device)
+            wb = int(_lib.lib().kcdc_inflate_workspace_size(n))
+            work = torch.empty(max(wb, 8), dtype=torch.uint8, device=device)
+        _lib.check(_lib.lib().kcdc_inflate_chunks_device(
             self.name.encode(), C.c_void_p(comp_ptr), d_offs.data_ptr(), d_lens.data_ptr(), n, d_out.data_ptr(),
             d_oo.data_ptr(), d_caps.data_ptr(), out_lens.data_ptr(), status.data_ptr(), work.data_ptr(), wb,
             C.c_void_p(stream.cuda_stream)))

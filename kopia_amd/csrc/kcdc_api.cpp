@@ -1055,3 +1055,32 @@ extern "C" int kcdc_decompress_chunks_device(const char* algorithm, const uint8_
     return launch_decompress(header_id, d_comp, d_offsets, d_comp_lens, nchunks, d_out, d_out_offsets, d_out_caps,
                              d_out_lens, d_status, d_work, work_bytes, hip_stream);
 }
+
+// ======================================================= inflate
+extern "C" int kcdc_inflate_algorithms(const char** names, int cap) { return comp_inflate_names(names, cap); }
+
+extern "C" uint64_t kcdc_inflate_workspace_size(uint32_t nchunks) { return inflate_workspace_size(nchunks); }
+
+extern "C" int kcdc_inflate_chunks_device(const char* algorithm, const uint8_t* d_comp, const uint64_t* d_offsets,
+                                          const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
+                                          const uint64_t* d_out_offsets, const uint64_t* d_out_caps,
+                                          uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes,
+                                          void* hip_stream) {
+    uint32_t header_id = 0;
+    bool gz = false;
+    const int found = comp_inflate_lookup(algorithm, &header_id, &gz);
+    if (found == -2)
+        return set_error(KCDC_ENOENT, std::string("unknown compression algorithm: ") + (algorithm ? algorithm : "(null)"));
+    if (found != 0)
+        return set_error(KCDC_EINVAL, std::string("compression algorithm ") + algorithm +
+                                          " is not a deflate stream (deflate-*, gzip* and pgzip* are inflated)");
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (int rc = check_device(dev)) return rc;
+    if (nchunks == 0) return KCDC_OK;
+    if (!d_comp || !d_offsets || !d_comp_lens || !d_out || !d_out_offsets || !d_out_caps || !d_out_lens || !d_status ||
+        !d_work)
+        return set_error(KCDC_EINVAL, "null argument");
+    return launch_inflate(header_id, gz, d_comp, d_offsets, d_comp_lens, nchunks, d_out, d_out_offsets, d_out_caps,
+                          d_out_lens, d_status, d_work, work_bytes, hip_stream);
+}

@@ -2834,6 +2834,23 @@ int comp_s2_names(const char** names, int cap) {
         }
     return n;
 }
+int comp_inflate_lookup(const char* name, uint32_t* header_id, bool* gz) {
+    const CompAlgo* a = find_comp(name);
+    if (!a) return -2;
+    if (a->fmt != compdev::kFmtDeflate) return -22;
+    *header_id = a->header_id;
+    *gz = a->gzip != 0;
+    return 0;
+}
+int comp_inflate_names(const char** names, int cap) {
+    int n = 0;
+    for (const CompAlgo& a : kCompAlgos)
+        if (a.fmt == compdev::kFmtDeflate) {
+            if (names && n < cap) names[n] = a.name;
+            n++;
+        }
+    return n;
+}
 int test_set_deflate_limit(bool cl, int64_t value) {
     if (value != 0 && (value < (cl ? 5 : 9) || value > (cl ? 7 : 15)))
         return set_error(-22, cl ? "deflate code-length code limit: 0 (default 7), or bits in [5, 7]"

@@ -35,7 +35,8 @@ using compdev::kCrc32cPoly;
 using compdev::multmodp;
 using s2f::Desc;
 
-constexpr uint32_t kPiece = 32768;   // CRC piece: 64 lanes of 512 bytes
+using compdev::kPiece;
+using compdev::piece_crc;
 constexpr uint32_t kCrcWaves = 4;
 constexpr uint32_t kDecodeWaves = 256u * 16u;  // the persistent grid: 16 waves for each of 256 CUs
 
@@ -201,32 +202,6 @@ __global__ __launch_bounds__(64) void decode_blocks_kernel(DecArgs a) {
     }
 }
 
-// Raw CRC-32C (register 0) of the `len` <= kPiece bytes at p by one wave: lanes take 512 bytes each,
-// counted back from the piece's end (bytes before it count as zeros, which a raw CRC ignores), and
-// combine in a 6-level tree with x^(2^(12+j)).  All lanes return the value of lane 0's tree.
-__device__ __forceinline__ uint32_t piece_crc(const uint8_t* p, uint32_t len, const uint32_t* tab,
-                                              const uint32_t* x2nc, uint32_t lane) {
-    const uint32_t sel = lane & 31u;
-    int32_t pos = static_cast<int32_t>(len) - static_cast<int32_t>(kPiece) + 512 * static_cast<int32_t>(lane);
-    const int32_t end = pos + 512;  // <= len
-    if (pos < 0) pos = 0;
-    uint32_t r = 0;
-    auto byte = [&](uint32_t v) { r = (r >> 8) ^ tab[32u * ((r ^ v) & 255u) + sel]; };
-    while (pos < end && (reinterpret_cast<uintptr_t>(p + pos) & 3u)) byte(p[pos++]);
-    for (; pos + 4 <= end; pos += 4) {
-        r ^= *reinterpret_cast<const uint32_t*>(p + pos);
-#pragma unroll
-        for (int t = 0; t < 4; t++) r = (r >> 8) ^ tab[32u * (r & 255u) + sel];
-    }
-    while (pos < end) byte(p[pos++]);
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        const uint32_t right = __shfl_down(r, 1u << j, 64);
-        if (((lane >> j) & 1u) == 0u) r = multmodp(r, x2nc[12 + j], kCrc32cPoly) ^ right;
-    }
-    return __shfl(r, 0, 64);
-}
-
 __global__ __launch_bounds__(64 * kCrcWaves) void decode_crc_kernel(DecArgs a) {
     __shared__ uint32_t tab[256 * 32];
     compdev::crc_table_fill(tab, kCrc32cPoly, 64u * kCrcWaves);
@@ -243,7 +218,7 @@ __global__ __launch_bounds__(64 * kCrcWaves) void decode_crc_kernel(DecArgs a) {
         uint32_t at = 0, raw = 0;
         for (uint32_t j = 0; j < pieces; j++) {
             const uint32_t plen = j == 0 ? d.out_len - (pieces - 1u) * kPiece : kPiece;
-            raw = multmodp(raw, a.x2nc[18], kCrc32cPoly) ^ piece_crc(p + at, plen, tab, a.x2nc, lane);
+            raw = multmodp(raw, a.x2nc[18], kCrc32cPoly) ^ piece_crc(p + at, plen, tab, a.x2nc, kCrc32cPoly, lane);
             at += plen;
         }
         const uint32_t crc = compdev::crc_finish(raw, d.out_len, a.x2nc, kCrc32cPoly);

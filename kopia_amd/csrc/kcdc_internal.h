@@ -135,6 +135,17 @@ int launch_decompress(uint32_t header_id, const uint8_t* d_comp, const uint64_t*
                       uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets, const uint64_t* d_out_caps,
                       uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
 
+// ---- inflate (kcdc_inflate.hip): the deflate-*, gzip* and pgzip* names
+// 0 with the name's header ID and whether its stream is wrapped in gzip members, -22 for a registered
+// name of another format, or -2 for an unregistered name.
+int comp_inflate_lookup(const char* name, uint32_t* header_id, bool* gz);
+int comp_inflate_names(const char** names, int cap);  // the nine names (sorted); returns their count
+uint64_t inflate_workspace_size(uint32_t nchunks);
+int launch_inflate(uint32_t header_id, bool gz, const uint8_t* d_comp, const uint64_t* d_offsets,
+                   const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets,
+                   const uint64_t* d_out_caps, uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes,
+                   void* stream);
+
 // ---- error correction (repo/ecc): parameters and geometry, shared by the host code and kcdc_ecc.hip
 #if defined(__HIPCC__)
 #define KCDC_HD __host__ __device__

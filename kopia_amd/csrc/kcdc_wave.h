@@ -1,6 +1,7 @@
-// Wave-level helpers shared by the compression and decompression kernels (kcdc_compress.hip,
-// kcdc_decompress.hip): the CRC shift machinery of zlib's crc32_combine (multmodp, the x^(2^k)
-// tables, the LDS byte table) and a copy of bytes at any alignment by one wave.
+// Wave-level helpers shared by the compression, decompression and inflate kernels
+// (kcdc_compress.hip, kcdc_decompress.hip, kcdc_inflate.hip): the CRC shift machinery of zlib's crc32_combine (multmodp, the x^(2^k)
+// tables, the LDS byte table, the CRC of a 32 KiB piece by one wave) and a copy of bytes at any
+// alignment by one wave.
 #pragma once
 
 #include <cstdint>
@@ -88,6 +89,37 @@ __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint
     }
     const uint32_t done = head + 4u * m;
     if (lane < n - done) dst[done + lane] = src[done + lane];
+}
+
+constexpr uint32_t kPiece = 32768;  // CRC piece: 64 lanes of 512 bytes
+// Raw CRC of `poly` (register 0) of the `len` <= kPiece bytes at p by one wave: lanes take 512 bytes each,
+// counted back from the piece's end (bytes before it count as zeros, which a raw CRC ignores), and
+// combine in a 6-level tree with x^(2^(12+j)).  All lanes return the value of lane 0's tree.
+__device__ __forceinline__ uint32_t piece_crc(const uint8_t* p, uint32_t len, const uint32_t* tab,
+                                              const uint32_t* x2nc, uint32_t poly, uint32_t lane) {
+    const uint32_t sel = lane & 31u;
+    int32_t pos = static_cast<int32_t>(len) - static_cast<int32_t>(kPiece) + 512 * static_cast<int32_t>(lane);
+    const int32_t end = pos + 512;  // <= len
+    if (pos < 0) pos = 0;
+    uint32_t r = 0;
+    auto byte = [&](uint32_t v) { r = (r >> 8) ^ tab[32u * ((r ^ v) & 255u) + sel]; };
+    while (pos < end && (reinterpret_cast<uintptr_t>(p + pos) & 3u)) byte(p[pos++]);
+    for (; pos + 4 <= end; pos += 4) {
+        r ^= *reinterpret_cast<const uint32_t*>(p + pos);
+#pragma unroll
+        for (int t = 0; t < 4; t++) r = (r >> 8) ^ tab[32u * (r & 255u) + sel];
+    }
+    while (pos < end) byte(p[pos++]);
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        const uint32_t right = __shfl_down(r, 1u << j, 64);
+        // the shift constant pinned in a VGPR: as a uniform value its 32-step chain of multiples is
+        // hoisted out of the caller's loop into SGPRs, six chains of them, and those spill
+        uint32_t shift = x2nc[12 + j];
+        asm volatile("" : "+v"(shift));
+        if (((lane >> j) & 1u) == 0u) r = multmodp(r, shift, poly) ^ right;
+    }
+    return __shfl(r, 0, 64);
 }
 #endif
 
