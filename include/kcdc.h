@@ -574,6 +574,13 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
  *                         ordinary skewed data.
  *   KCDC_TEST_DEFLATE_CL_MAXB the same for the dynamic header's code-length code, in [5, 7]; 0: the
  *                         default (7)
+ *   KCDC_TEST_CHUNK_GRID  the most workgroups the persistent per-chunk kernels are launched with:
+ *                         the unit passes of kcdc_encrypt / kcdc_decrypt_chunks_device, the block
+ *                         decode of kcdc_decompress_chunks_device and the content decode of
+ *                         kcdc_inflate_chunks_device (their CRC passes follow); 0: the default (no
+ *                         cap); negative: KCDC_EINVAL.  Same results from any grid: with one
+ *                         workgroup a few hundred tiny chunks make every wave walk many chunks and
+ *                         take many tickets, which otherwise needs tens of thousands.
  * kcdc_test_long_stat: after the last long-stream launch made with KCDC_TEST_LONG_STAT on has
  * finished (synchronise first): KCDC_TEST_LONG_STREAMS, the streams of that launch, or
  * KCDC_TEST_LONG_SERIAL, how many of them the serial resolver took (truncated segments, or no
@@ -609,6 +616,7 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
 #define KCDC_TEST_LONG_STAT 11
 #define KCDC_TEST_DEFLATE_MAXB 12
 #define KCDC_TEST_DEFLATE_CL_MAXB 13
+#define KCDC_TEST_CHUNK_GRID 14
 int kcdc_test_set(int32_t key, int64_t value);
 #define KCDC_TEST_LONG_STREAMS 1
 #define KCDC_TEST_LONG_SERIAL 2

@@ -98,14 +98,16 @@ class Compressor:
         return out_lens[:n], ids[:n]
 
     def decompress_chunks_device(self, comp_ptr: int, offsets, lengths, d_out, out_offsets, out_caps, device,
-                                 stream=None):
+                                 stream=None, work_bytes: int | None = None):
         """Decompress content i = [offsets[i], +lengths[i]) of the device bytes at comp_ptr (the
         4-byte header ID, then the stream, as compress_chunks_device writes them) into d_out (a
         device uint8 tensor) at out_offsets[i], at most out_caps[i] bytes.
         Returns device tensors (out_lens int64, status int32): status[i] is 0 with out_lens[i] the
         decoded length, or KCDC_EBADMSG (wrong header ID, malformed stream, CRC mismatch),
         KCDC_EOVERFLOW (longer than the cap) or KCDC_ENOMEM (more data chunks than one per 16 KiB
-        of cap, plus one) with out_lens[i] = 0.  Asynchronous on `stream`."""
+        of cap, plus one) with out_lens[i] = 0.  work_bytes: a workspace larger than
+        kcdc_decompress_workspace_size, for contents with more data chunks than that (every content
+        gets an equal share of the extra descriptors).  Asynchronous on `stream`."""
         import torch
         n = len(offsets)
         if stream is None:
@@ -122,6 +124,8 @@ class Compressor:
             d_oo = torch.as_tensor(np.asarray(out_offsets, dtype=np.int64)).to(device)
             d_caps = torch.as_tensor(caps).to(device)
             wb = int(_lib.lib().kcdc_decompress_workspace_size(int(lens.sum()), int(caps.sum()), n))
+            if work_bytes is not None:
+                wb = int(work_bytes)
             work = torch.empty(max(wb, 8), dtype=torch.uint8, device=device)
         _lib.check(_lib.lib().kcdc_decompress_chunks_device(
             self.name.encode(), C.c_void_p(comp_ptr), d_offs.data_ptr(), d_lens.data_ptr(), n, d_out.data_ptr(),

@@ -1470,8 +1470,9 @@ int crypt_run(const char* name, const uint8_t* secret, uint32_t secret_len, cons
     const WsLayout l = ws_layout(n);
     if (work_bytes < l.total) return set_error(-22, "workspace too small (kcdc_crypt_workspace_size)");
     int err = 0;
-    const int grid = units_grid(&err);
+    int grid = units_grid(&err);
     if (err) return err;
+    grid = static_cast<int>(cap_chunk_grid(static_cast<uint32_t>(grid)));  // KCDC_TEST_CHUNK_GRID
 
     cryptdev::CryptArgs a{};
     a.n = n;
@@ -1509,8 +1510,9 @@ int crypt_run(const char* name, const uint8_t* secret, uint32_t secret_len, cons
     if (std::strcmp(name, "AES256-GCM-HMAC-SHA256") == 0) {
         static_assert(sizeof(cryptdev::GcmKey) <= sizeof(ChunkKey) + kTabN * sizeof(Fe), "GcmKey fits the ChaCha slots");
         cryptdev::GcmKey* gk = reinterpret_cast<cryptdev::GcmKey*>(w + l.keys);
-        const int ggrid = gcm_grid(&err);
+        int ggrid = gcm_grid(&err);
         if (err) return err;
+        ggrid = static_cast<int>(cap_chunk_grid(static_cast<uint32_t>(ggrid)));
         hipLaunchKernelGGL(cryptdev::gcm_prep_kernel<kOpen>, dim3((n + 3u) / 4u), dim3(256), 0, st, a, gk);
         hipLaunchKernelGGL(cryptdev::unit_scan_kernel, dim3(1), dim3(1024), 0, st, n, a.units);
         hipLaunchKernelGGL(cryptdev::gcm_units_kernel<kOpen>, dim3(ggrid), dim3(64 * cryptdev::kGcmWaves), 0, st, a, gk, gk, a.units);

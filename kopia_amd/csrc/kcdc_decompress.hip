@@ -284,7 +284,8 @@ int launch_decompress(uint32_t header_id, const uint8_t* d_comp, const uint64_t*
     hipLaunchKernelGGL(decdev::decode_index_kernel, dim3((nchunks + 63u) / 64u), dim3(64), 0, st, a);
     hipLaunchKernelGGL(decdev::decode_scan_kernel<decdev::kScanBlocks>, dim3(1), dim3(1024), 0, st, a);
     if (a.max_desc > 0) {
-        const uint32_t waves = static_cast<uint32_t>(a.max_desc < decdev::kDecodeWaves ? a.max_desc : decdev::kDecodeWaves);
+        const uint32_t waves = cap_chunk_grid(  // KCDC_TEST_CHUNK_GRID
+            static_cast<uint32_t>(a.max_desc < decdev::kDecodeWaves ? a.max_desc : decdev::kDecodeWaves));
         hipLaunchKernelGGL(decdev::decode_blocks_kernel, dim3(waves), dim3(64), 0, st, a);
         hipLaunchKernelGGL(decdev::decode_crc_kernel, dim3((waves + decdev::kCrcWaves - 1u) / decdev::kCrcWaves),
                            dim3(64 * decdev::kCrcWaves), 0, st, a);

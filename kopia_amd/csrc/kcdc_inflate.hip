@@ -369,7 +369,7 @@ int launch_inflate(uint32_t header_id, bool gz, const uint8_t* d_comp, const uin
     a.gz = gz ? 1u : 0u;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(infdev::inflate_init_kernel, dim3(1), dim3(64), 0, st, a);
-    const uint32_t waves = nchunks < infdev::kInflateWaves ? nchunks : infdev::kInflateWaves;
+    const uint32_t waves = cap_chunk_grid(nchunks < infdev::kInflateWaves ? nchunks : infdev::kInflateWaves);  // KCDC_TEST_CHUNK_GRID
     hipLaunchKernelGGL(infdev::inflate_kernel, dim3(waves), dim3(64), 0, st, a);
     if (gz)
         hipLaunchKernelGGL(infdev::inflate_crc_kernel, dim3((waves + infdev::kCrcWaves - 1u) / infdev::kCrcWaves),

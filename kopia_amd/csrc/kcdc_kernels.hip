@@ -775,6 +775,11 @@ int launch_split_long(const Algo& algo, const uint8_t* d_data, uint64_t len, uin
 }
 
 // ------------------------------------------------------------------ testing
+uint32_t& test_chunk_grid() {
+    static uint32_t cap = 0;
+    return cap;
+}
+
 extern "C" int64_t kcdc_test_server_requests(void) { return static_cast<int64_t>(scan_server_requests()); }
 
 extern "C" int kcdc_test_set(int32_t key, int64_t value) {
@@ -805,6 +810,10 @@ extern "C" int kcdc_test_set(int32_t key, int64_t value) {
         case 11: g_test.long_stat = value != 0; return 0;                  // KCDC_TEST_LONG_STAT
         case 12: return test_set_deflate_limit(false, value);              // KCDC_TEST_DEFLATE_MAXB
         case 13: return test_set_deflate_limit(true, value);               // KCDC_TEST_DEFLATE_CL_MAXB
+        case 14:                                                           // KCDC_TEST_CHUNK_GRID
+            if (value < 0) return set_error(-22, "chunk grid: 0 (default), or workgroups >= 1");
+            test_chunk_grid() = static_cast<uint32_t>(value < 0x7fffffff ? value : 0x7fffffff);  // above any grid
+            return 0;
         default: return set_error(-22, "unknown test knob");
     }
 }

@@ -35,10 +35,10 @@ def checked():
     return res
 
 
-def _decompress(name, blobs, caps, dev):
+def _decompress(name, blobs, caps, dev, work_bytes=None):
     """Decode `blobs` in one call: contents packed at odd offsets, output slots at odd offsets with
     a guard before and after each.  Returns (output bytes, slot offsets, lengths, statuses) after
-    checking every byte outside the slots."""
+    checking every byte outside the slots.  work_bytes: a workspace above the minimum size."""
     import torch
     comp, offs = bytearray(), []
     for i, b in enumerate(blobs):  # content i starts at an odd offset: 1, 3, 5, 7 mod 8 in turn
@@ -55,7 +55,7 @@ def _decompress(name, blobs, caps, dev):
     d_comp = torch.from_numpy(np.frombuffer(bytes(comp), np.uint8).copy()).to(dev)
     d_out = torch.full((total,), GUARD, dtype=torch.uint8, device=dev)
     lens, st = kc.Compressor(name).decompress_chunks_device(d_comp.data_ptr(), offs, [len(b) for b in blobs], d_out,
-                                                            out_offs, caps, dev)
+                                                            out_offs, caps, dev, work_bytes=work_bytes)
     torch.cuda.synchronize()
     out = d_out.cpu().numpy()
     outside = np.ones(total, bool)
@@ -125,6 +125,42 @@ def test_corrupt_contents_among_good_ones(gpu, checked):
     out, out_offs, lens, st = _decompress(sv.NAME, [v.blob for v in vs], [v.cap for v in vs], gpu)
     _expect(vs, out, out_offs, lens, st)
     seen = {v.status for v in bad}
+    assert seen == {sv.EBADMSG, sv.EOVERFLOW, sv.ENOMEM}
+
+
+@pytest.fixture
+def chunk_grid(request):
+    """At most this many workgroups (waves) in the persistent block decode (KCDC_TEST_CHUNK_GRID)."""
+    L = _lib.lib()
+    assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, request.param) == 0
+    yield request.param
+    assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, 0) == 0
+
+
+@pytest.mark.parametrize("chunk_grid", (1, 3), indirect=True)
+def test_one_wave_decodes_every_vector(chunk_grid, gpu, checked):
+    """One wave (or three) takes every block ticket of a call, in block order with one: every valid
+    vector of at most 70,000 decoded bytes, per header ID, a corrupt one after each good one while
+    they last (a workspace of the minimum size, as the corrupt vectors' statuses assume).  The wave
+    that has just refused a block decodes the next content's block with the input window and repeat
+    offset it still holds: every content exact, guards intact."""
+    seen, took_part = set(), 0
+    for name in sorted({v.name for v in sv.valid_vectors()}):
+        good = [v for v in sv.valid_vectors() if v.name == name and len(v.expected) <= 70000]
+        bad = [v for v in sv.corrupt_vectors() if v.name == name]
+        if not good:
+            assert not bad
+            continue
+        assert len(good) > len(bad)
+        vs = []
+        for i, g in enumerate(good):
+            vs += [g] + bad[i:i + 1]
+        assert {v.id for v in bad} <= {v.id for v in vs}
+        out, out_offs, lens, st = _decompress(name, [v.blob for v in vs], [v.cap for v in vs], gpu)
+        _expect(vs, out, out_offs, lens, st)
+        seen |= {v.status for v in bad}
+        took_part += len(good)
+    assert took_part >= 55
     assert seen == {sv.EBADMSG, sv.EOVERFLOW, sv.ENOMEM}
 
 

@@ -158,6 +158,39 @@ def test_more_contents_than_waves(gpu):
             assert out[out_offs[i]:out_offs[i] + size].tobytes() == parts[i], i
 
 
+@pytest.fixture
+def chunk_grid(request):
+    """At most this many workgroups (waves) in the persistent decode kernel (KCDC_TEST_CHUNK_GRID)."""
+    L = _lib.lib()
+    assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, request.param) == 0
+    yield request.param
+    assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, 0) == 0
+
+
+@pytest.mark.parametrize("chunk_grid", (1, 3), indirect=True)
+def test_one_wave_decodes_every_vector(chunk_grid, gpu, checked):
+    """One wave (or three) takes every ticket of a call, in content order with one: every valid
+    vector of at most 70,000 decoded bytes, a corrupt one after each good one while they last.  So the
+    wave that has just refused a content, or finished a stored, fixed or dynamic block, decodes the
+    next content of another block type with whatever LDS tables, bit window and status it still
+    holds: every content exact, guards intact."""
+    seen, took_part = set(), 0
+    for name in iv.FAMILIES:
+        good = [v for v in iv.valid_vectors() if v.name == name and len(v.expected) <= 70000]
+        bad = [v for v in iv.corrupt_vectors() if v.name == name]
+        assert len(good) > len(bad) > 0
+        vs = []
+        for i, g in enumerate(good):
+            vs += [g] + bad[i:i + 1]
+        assert {v.id for v in bad} <= {v.id for v in vs}
+        out, out_offs, lens, st = _inflate(name, [v.blob for v in vs], [v.cap for v in vs], gpu)
+        _expect(vs, out, out_offs, lens, st)
+        seen |= {v.status for v in bad}
+        took_part += len(good)
+    assert took_part >= 150
+    assert seen == {iv.EBADMSG, iv.EOVERFLOW}
+
+
 def test_argument_errors(gpu):
     import torch
     L = _lib.lib()

@@ -118,6 +118,20 @@ def test_batch_plan_hook_refuses_what_has_no_plan():
     assert list(out) == [7, 7, 7, 7]
 
 
+def test_chunk_grid_hook_needs_no_device():
+    """kcdc_test_set(KCDC_TEST_CHUNK_GRID): any positive cap is taken, a negative one is refused with
+    the cap unchanged, 0 restores the default; host state only, no device is touched."""
+    L = _lib.lib()
+    try:
+        for v in (1, 3, 1 << 20, 1 << 40):
+            assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, v) == 0, v
+        for v in (-1, -(1 << 40)):
+            assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, v) == _lib.KCDC_EINVAL, v
+            assert "chunk grid" in _lib.last_error()
+    finally:
+        assert L.kcdc_test_set(_lib.TEST_CHUNK_GRID, 0) == 0
+
+
 def test_fixed_streaming_handle_needs_no_device():
     """FIXED reads no data (splitter_fixed.go:15-26): pure host arithmetic."""
     s = ks.GetFactory("FIXED-128K")()
