@@ -307,7 +307,8 @@ int kcdc_gorand_read(int64_t seed, uint8_t* out, uint64_t n);
  *   size, a multiple of 4).  key: the repository's HMAC secret (<= 64 bytes for BLAKE2B,
  *   <= 32 for BLAKE2S; BLAKE2S-128 needs one, as blake2s.New128 does).  d_order: optional
  *   processing order (e.g. chunk indices by descending length: a wave runs until its
- *   longest chunk is done), NULL = as given.  Asynchronous on hip_stream. */
+ *   longest chunk is done), NULL = as given.  Offsets, lengths and the hashes' byte counters are
+ *   64 bits: neither has a limit at 2^32.  Asynchronous on hip_stream. */
 int kcdc_hash_algorithms(const char** names, int cap);
 int kcdc_hash_size(const char* hash_name);
 int kcdc_hash_chunks_device(const char* hash_name, const uint8_t* d_data, const uint64_t* d_offsets,
@@ -382,7 +383,9 @@ int kcdc_decrypt_chunks_device(const char* algorithm, const uint8_t* secret, uin
  * kcdc_compress_chunks_device: chunk i = [d_offsets[i], +d_lens[i]) of d_data (any alignment);
  *   out_i goes to d_out + d_out_offsets[i] (room for kcdc_compress_bound bytes), its length to
  *   d_out_lens[i] and id_i to d_header_ids[i].  A workspace too small for the chunks' spans
- *   leaves every d_out_lens[i] = 0.  Asynchronous on hip_stream. */
+ *   leaves every d_out_lens[i] = 0.  Offsets and lengths are 64 bits with no limit at 2^32 (a
+ *   gzip member's ISIZE is the length mod 2^32, RFC 1952); a call holds fewer than 2^32 spans of
+ *   32 KiB.  Asynchronous on hip_stream. */
 int kcdc_compression_algorithms(const char** names, int cap);
 int64_t kcdc_compression_header_id(const char* algorithm);
 uint64_t kcdc_compress_bound(uint64_t len);
@@ -419,6 +422,8 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
  *   the slot's contents are unspecified; no byte outside [d_out_offsets[i], +d_out_caps[i]) is
  *   written, the content's compressed bytes are read through aligned 4-byte words that hold at least
  *   one of them, and no other content of the call is affected.  d_work: 8-byte aligned.
+ *   Offsets, d_comp_lens and d_out_caps are 64 bits with no limit at 2^32 (a block decodes to at
+ *   most 4 MiB); a cap above 4 GiB takes the workspace kcdc_decompress_workspace_size gives for it.
  *   Returns KCDC_ENOENT for an unknown name, KCDC_EINVAL for a registered compressor with no
  *   device decoder (deflate-*, gzip*, pgzip*, zstd*).  Asynchronous on hip_stream: no host
  *   synchronisation and no copy to the host; d_work must stay allocated until the work finishes.
@@ -505,7 +510,10 @@ int kcdc_inflate_chunks_device(const char* algorithm, const uint8_t* d_comp, con
  *   failed (d_out_lens[i] = 0, the slot holds unverified bytes: call the repair);
  *   KCDC_EBADMSG if the in-band length exceeds what the stored bytes hold (slot zeroed);
  *   KCDC_EINVAL if stored_len < 40, the smallest stored size; KCDC_ENOMEM if d_work is too
- *   small for the chunk's blocks.  Asynchronous on hip_stream.
+ *   small for the chunk's blocks.  Offsets and stored lengths are 64 bits with no limit at 2^32
+ *   (the in-band length is below it by construction); the host's kcdc_ecc_decoded_bound refuses a
+ *   stored_len above 2^40 with KCDC_EFBIG, the device call has no check of its own there.
+ *   Asynchronous on hip_stream.
  * kcdc_ecc_repair_chunks_device: ReconstructData (ecc_rs_crc.go:325) for the chunks a decode call
  *   with the same arguments left KCDC_ECC_DAMAGED.  Waits for hip_stream, reads back the statuses
  *   and the bad-shard masks, inverts one matrix per erasure pattern on the host, rebuilds the
