@@ -5,11 +5,11 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 CSRC := kopia_amd/csrc
 OBJ := build/obj
-SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_inflate.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
+SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_inflate.hip $(CSRC)/kcdc_zstd.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 LIB := kopia_amd/libkcdc.so
 
-all: $(LIB) oracle build/writer_bench build/s2_decode_host build/inflate_host
+all: $(LIB) oracle build/writer_bench build/s2_decode_host build/inflate_host build/zstd_decode_host
 
 # every object depends on every header of the sources' directory: a header edit rebuilds
 HDRS := $(wildcard $(CSRC)/*.h) include/kcdc.h
@@ -79,6 +79,12 @@ build/s2_decode_host: tools/s2_decode_host.cpp $(CSRC)/kcdc_s2_format.h $(CSRC)/
 # The inflate decoder's validity header on the CPU under the host sanitizers
 # (tests/test_inflate_vectors.py runs every vector through it before the GPU sees one)
 build/inflate_host: tools/inflate_host.cpp $(CSRC)/kcdc_inflate_format.h
+	@mkdir -p build
+	g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan -I$(CSRC) $< -o $@
+
+# The zstd decoder's validity header on the CPU under the host sanitizers
+# (tests/test_zstd_vectors.py runs every vector through it before the GPU sees one)
+build/zstd_decode_host: tools/zstd_decode_host.cpp $(CSRC)/kcdc_zstd_format.h
 	@mkdir -p build
 	g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan -I$(CSRC) $< -o $@
 

@@ -427,7 +427,8 @@ int kcdc_compress_chunks_device(const char* algorithm, const uint8_t* d_data, co
  *   Returns KCDC_ENOENT for an unknown name, KCDC_EINVAL for a registered compressor with no
  *   device decoder (deflate-*, gzip*, pgzip*, zstd*).  Asynchronous on hip_stream: no host
  *   synchronisation and no copy to the host; d_work must stay allocated until the work finishes.
- *   The deflate-*, gzip* and pgzip* names are decoded by the kcdc_inflate_* family below. */
+ *   The deflate-*, gzip* and pgzip* names are decoded by the kcdc_inflate_* family below, the
+ *   zstd* names by the kcdc_zstd_decode_* family after it. */
 int kcdc_decompression_algorithms(const char** names, int cap);
 uint64_t kcdc_decompress_workspace_size(uint64_t total_compressed_bytes, uint64_t total_out_cap_bytes,
                                         uint32_t nchunks);
@@ -473,6 +474,56 @@ int kcdc_inflate_chunks_device(const char* algorithm, const uint8_t* d_comp, con
                                const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
                                const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_lens,
                                int32_t* d_status, void* d_work, uint64_t work_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------- zstd decoding
+ * The same step of the read path (c.Decompress, repo/content/committed_read_manager.go:336) for the
+ * four zstd* compressors: zstdCompressor.Decompress (compressor_zstd.go:73-91:
+ * verifyCompressionHeader, then zstd.NewReader over the rest):
+ *   content_i = BE32(header ID) || RFC 8878 frames
+ * from any writer, not only kcdc_compress_chunks_device, without a dictionary: any number of frames
+ * with their output appended, skippable frames anywhere among them, both Single_Segment forms, every
+ * Frame_Content_Size width (checked against the decoded length), Window_Descriptor from 1 KiB up,
+ * a Dictionary_ID field only when it holds 0, Content_Checksum (the low 32 bits of XXH64, seed 0)
+ * verified when flagged; raw, RLE and compressed blocks; Raw, RLE, Compressed and Treeless literals
+ * in every size format with 1 or 4 streams; all three Number_of_Sequences encodings and the
+ * Predefined, RLE, FSE_Compressed and Repeat modes of each table; repeat offsets carried across the
+ * blocks of a frame.  A match offset may reach neither before its own frame's first byte nor
+ * beyond Window_Size.  The choices made where libzstd and Go's reader differ are listed in
+ * kopia_amd/csrc/kcdc_zstd_format.h.
+ * kcdc_zstd_decode_algorithms: the four names, sorted.
+ * kcdc_zstd_decode_workspace_size: device scratch for nchunks contents whose output slots hold
+ *   total_out_cap_bytes in all.  Content i gets, at places fixed before any of its bytes is read:
+ *   a literal room of d_out_caps[i] bytes (a content's literals cannot exceed its decoded length),
+ *   a sequence room of d_out_caps[i] / 3 + 1 records of 12 bytes (every sequence yields at least 3
+ *   bytes), and 4 + d_out_caps[i] / 1 KiB descriptors of 32 bytes, one per block and one per frame
+ *   (1 KiB is the smallest Block_Maximum_Size), plus an equal share of whatever descriptor room a
+ *   larger work_bytes gives beyond that; 36 bytes per content and fixed fields besides.
+ *   Writers that fill their blocks fit; this library's own zstd-fastest frames hold a block per 512
+ *   bytes and need d_out_caps[i] / 512 more descriptors for every content.
+ *   total_compressed_bytes does not enter.
+ * kcdc_zstd_decode_chunks_device: the arguments and the contract of kcdc_decompress_chunks_device.
+ *   d_status[i]: 0 with d_out_lens[i] the decoded length; KCDC_EBADMSG for a wrong header ID, a
+ *   malformed or truncated frame, a content-size or checksum mismatch; KCDC_EOVERFLOW if the decoded
+ *   bytes would exceed d_out_caps[i] (a content whose headers ask for more literal or sequence room
+ *   than the cap grants decodes past the cap by that fact alone); KCDC_ENOMEM if the content has
+ *   more blocks and frames than its descriptors, or if work_bytes is below what
+ *   kcdc_zstd_decode_workspace_size gives for the caps actually passed (then every content gets
+ *   it).  On a failure d_out_lens[i] = 0 and the slot's contents are unspecified; no byte outside
+ *   the slot and none outside [d_work, +work_bytes) is written, and no other content of the call is
+ *   affected.  Positions are 32 bits on the device: a content of 4 GiB or more gets KCDC_EBADMSG,
+ *   a cap above 4 GiB - 1 counts as 4 GiB - 1, and a content that would decode past 4 GiB - 1 gets
+ *   KCDC_EOVERFLOW.  d_work: 8-byte aligned.  Returns KCDC_ENOENT for an unknown name, KCDC_EINVAL
+ *   for a registered name of another format (s2-*, deflate-*, gzip*, pgzip*), a null argument, or
+ *   a workspace below kcdc_zstd_decode_workspace_size(0, 0, nchunks) or misaligned, KCDC_ENODEV
+ *   without a device.  nchunks == 0 launches nothing.  Asynchronous on hip_stream: no host
+ *   synchronisation and no copy to the host; d_work must stay allocated until the work finishes. */
+int kcdc_zstd_decode_algorithms(const char** names, int cap);
+uint64_t kcdc_zstd_decode_workspace_size(uint64_t total_compressed_bytes, uint64_t total_out_cap_bytes,
+                                         uint32_t nchunks);
+int kcdc_zstd_decode_chunks_device(const char* algorithm, const uint8_t* d_comp, const uint64_t* d_offsets,
+                                   const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
+                                   const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_lens,
+                                   int32_t* d_status, void* d_work, uint64_t work_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------- error correction
  * Kopia's ECC layer for many chunks per call: repo/ecc, REED-SOLOMON-CRC32 (ecc_rs_crc.go).  A
@@ -585,7 +636,9 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
  *   KCDC_TEST_CHUNK_GRID  the most workgroups the persistent per-chunk kernels are launched with:
  *                         the unit passes of kcdc_encrypt / kcdc_decrypt_chunks_device, the block
  *                         decode of kcdc_decompress_chunks_device and the content decode of
- *                         kcdc_inflate_chunks_device (their CRC passes follow); 0: the default (no
+ *                         kcdc_inflate_chunks_device (their CRC passes follow), and the entropy and
+ *                         execute passes of kcdc_zstd_decode_chunks_device (zstd_entropy_kernel,
+ *                         zstd_execute_kernel; its checksum pass follows); 0: the default (no
  *                         cap); negative: KCDC_EINVAL.  Same results from any grid: with one
  *                         workgroup a few hundred tiny chunks make every wave walk many chunks and
  *                         take many tickets, which otherwise needs tens of thousands.

@@ -41,7 +41,7 @@ TEST_LONG_STAT = 11
 # deflate plan limits (tests/test_gpu_deflate_edges.py): longest literal/length and distance code, 9..15
 # (0: 15), and longest code-length code, 5..7 (0: 7); a lower limit still gives a valid RFC 1951 stream
 TEST_DEFLATE_MAXB, TEST_DEFLATE_CL_MAXB = 12, 13
-# the most workgroups of the persistent per-chunk kernels (crypt units, S2 block decode, inflate); 0: no cap
+# the most workgroups of the persistent per-chunk kernels (crypt units, S2 block decode, inflate, zstd entropy and execute); 0: no cap
 TEST_CHUNK_GRID = 14
 LONG_STREAMS, LONG_SERIAL = 1, 2  # kcdc_test_long_stat keys
 STAT_GIVEUPS, STAT_DONE, STAT_STEALS, STAT_HELPS, STAT_TICKET_AUDIT = 1, 2, 3, 4, 5
@@ -139,6 +139,10 @@ _SIGS = {
                                                 _P]),
     "kcdc_inflate_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),
     "kcdc_inflate_workspace_size": (C.c_uint64, [C.c_uint32]),
+    "kcdc_zstd_decode_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),
+    "kcdc_zstd_decode_workspace_size": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "kcdc_zstd_decode_chunks_device": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                                 _P]),
     "kcdc_inflate_chunks_device": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
                                              _P]),
     "kcdc_ecc_algorithms": (C.c_int, [C.POINTER(C.c_char_p), C.c_int]),

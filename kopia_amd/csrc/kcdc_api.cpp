@@ -1084,3 +1084,36 @@ extern "C" int kcdc_inflate_chunks_device(const char* algorithm, const uint8_t* 
     return launch_inflate(header_id, gz, d_comp, d_offsets, d_comp_lens, nchunks, d_out, d_out_offsets, d_out_caps,
                           d_out_lens, d_status, d_work, work_bytes, hip_stream);
 }
+
+// ======================================================= zstd decoding
+// zstd.NewReader behind compressor_zstd.go:73-91 (Decompress), for many contents per call.
+extern "C" int kcdc_zstd_decode_algorithms(const char** names, int cap) { return comp_zstd_names(names, cap); }
+
+extern "C" uint64_t kcdc_zstd_decode_workspace_size(uint64_t total_compressed_bytes, uint64_t total_out_cap_bytes,
+                                                    uint32_t nchunks) {
+    (void)total_compressed_bytes;  // every room is counted by output: literals, sequences and blocks alike
+    return zstd_decode_workspace_size(total_out_cap_bytes, nchunks);
+}
+
+extern "C" int kcdc_zstd_decode_chunks_device(const char* algorithm, const uint8_t* d_comp, const uint64_t* d_offsets,
+                                              const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out,
+                                              const uint64_t* d_out_offsets, const uint64_t* d_out_caps,
+                                              uint64_t* d_out_lens, int32_t* d_status, void* d_work,
+                                              uint64_t work_bytes, void* hip_stream) {
+    uint32_t header_id = 0;
+    const int found = comp_zstd_lookup(algorithm, &header_id);
+    if (found == -2)
+        return set_error(KCDC_ENOENT, std::string("unknown compression algorithm: ") + (algorithm ? algorithm : "(null)"));
+    if (found != 0)
+        return set_error(KCDC_EINVAL, std::string("compression algorithm ") + algorithm +
+                                          " is not a zstd stream (the four zstd* names are decoded here)");
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (int rc = check_device(dev)) return rc;
+    if (nchunks == 0) return KCDC_OK;
+    if (!d_comp || !d_offsets || !d_comp_lens || !d_out || !d_out_offsets || !d_out_caps || !d_out_lens || !d_status ||
+        !d_work)
+        return set_error(KCDC_EINVAL, "null argument");
+    return launch_zstd_decode(header_id, d_comp, d_offsets, d_comp_lens, nchunks, d_out, d_out_offsets, d_out_caps,
+                              d_out_lens, d_status, d_work, work_bytes, hip_stream);
+}

@@ -2851,6 +2851,22 @@ int comp_inflate_names(const char** names, int cap) {
         }
     return n;
 }
+int comp_zstd_lookup(const char* name, uint32_t* header_id) {
+    const CompAlgo* a = find_comp(name);
+    if (!a) return -2;
+    if (a->fmt != compdev::kFmtZstd) return -22;
+    *header_id = a->header_id;
+    return 0;
+}
+int comp_zstd_names(const char** names, int cap) {
+    int n = 0;
+    for (const CompAlgo& a : kCompAlgos)
+        if (a.fmt == compdev::kFmtZstd) {
+            if (names && n < cap) names[n] = a.name;
+            n++;
+        }
+    return n;
+}
 int test_set_deflate_limit(bool cl, int64_t value) {
     if (value != 0 && (value < (cl ? 5 : 9) || value > (cl ? 7 : 15)))
         return set_error(-22, cl ? "deflate code-length code limit: 0 (default 7), or bits in [5, 7]"

@@ -44,7 +44,7 @@ int& test_hash_lanes();
 int test_set_deflate_limit(bool cl, int64_t value);  // kcdc_test_set(KCDC_TEST_DEFLATE_MAXB / _CL_MAXB)
 uint64_t& test_id_ring_bytes();  // kcdc_test_set(KCDC_TEST_ID_RING): the writers' ID ring size (0: default)
 // kcdc_test_set(KCDC_TEST_CHUNK_GRID): the most workgroups a persistent per-chunk kernel is launched
-// with (crypt_units / gcm_units, decode_blocks, inflate); 0: no cap.
+// with (crypt_units / gcm_units, decode_blocks, inflate, zstd_entropy, zstd_execute); 0: no cap.
 uint32_t& test_chunk_grid();
 inline uint32_t cap_chunk_grid(uint32_t grid) {
     const uint32_t cap = test_chunk_grid();
@@ -152,6 +152,16 @@ int launch_inflate(uint32_t header_id, bool gz, const uint8_t* d_comp, const uin
                    const uint64_t* d_comp_lens, uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets,
                    const uint64_t* d_out_caps, uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes,
                    void* stream);
+
+// ---- zstd decoding (kcdc_zstd.hip): the four zstd* names
+// 0 with the name's header ID, -22 for a registered name of another format, or -2 for an
+// unregistered name.
+int comp_zstd_lookup(const char* name, uint32_t* header_id);
+int comp_zstd_names(const char** names, int cap);  // the four names (sorted); returns their count
+uint64_t zstd_decode_workspace_size(uint64_t total_out_cap_bytes, uint32_t nchunks);
+int launch_zstd_decode(uint32_t header_id, const uint8_t* d_comp, const uint64_t* d_offsets, const uint64_t* d_comp_lens,
+                       uint32_t nchunks, uint8_t* d_out, const uint64_t* d_out_offsets, const uint64_t* d_out_caps,
+                       uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
 
 // ---- error correction (repo/ecc): parameters and geometry, shared by the host code and kcdc_ecc.hip
 #if defined(__HIPCC__)
