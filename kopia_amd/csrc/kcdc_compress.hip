@@ -1022,8 +1022,8 @@ __device__ uint32_t zstd_seqs(uint8_t* sb8, uint32_t o, uint32_t nseq, uint32_t 
 // (match length - 4) << 15 | distance) and their count in the span's descriptor.  zstd_emit_kernel
 // (one workgroup per span) then writes the span as kZBlks Compressed_Blocks, runs of segments of
 // about equal sequence counts (RFC 8878 §3.1.1.2), all sharing the span's codes:
-//   literals   one Huffman code for the span (<= 11 bits, direct weights: the largest literal
-//              must be <= 128), its tree carried by the span's first compressed block that uses it
+//   literals   one Huffman code for the span (<= 11 bits; its weights direct or FSE-compressed,
+//              the smaller, FSE alone above symbol 128), its tree carried by the span's first compressed block that uses it
 //              (Compressed_Literals_Block), the later ones Treeless; 1 stream up to 1023 literals,
 //              else 4 (jump table); a block whose raw literals are smaller keeps them raw;
 //   sequences  three FSE tables (literal length, offset, match length codes) normalized from the

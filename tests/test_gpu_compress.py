@@ -236,13 +236,9 @@ def test_mixed_ratio_does_not_regress(gpu):
     assert ratio["s2-default"] <= 1.25 * z6 and ratio["zstd"] <= 1.26 * z6, (ratio, z6)
 
 
-@pytest.mark.parametrize("name", ["zstd", "zstd-best-compression"])
-def test_zstd_table_carriers(name, gpu):
-    """Spans whose blocks (16 segments each) mix Raw_Blocks with compressed ones: the Huffman tree
-    and the FSE tables must ride on the first COMPRESSED block that uses them (a raw block 0, a
-    raw block between compressed ones, a literal-free block 0), later blocks reuse them (Treeless
-    literals, Repeat_Mode tables), and repeat offsets never reach back across a raw block.  Text
-    with literals above 128 takes the FSE-compressed weights description (RFC 8878 §4.2.1.2)."""
+def table_carrier_chunks():
+    """The chunks of test_zstd_table_carriers (tools/zstd_census.py reports which branches of the span
+    encoder they reach)."""
     rng = np.random.default_rng(77)
     rnd = lambda n: rng.integers(0, 256, n, dtype=np.uint8)
     text = lambda n: _mixed(n, int(rng.integers(1 << 30)))[:n]
@@ -262,7 +258,37 @@ def test_zstd_table_carriers(name, gpu):
         [hitext(40000)],                                       # literals > 128: FSE-compressed weights
         [rnd(3000), hitext(30000), rnd(100)],                  # every byte value in the span's code
     ]
-    chunks = [np.concatenate(p) for p in parts]
+    return [np.concatenate(p) for p in parts]
+
+
+def adversarial_parts():
+    """The chunks of test_zstd_adversarial_spans (tools/zstd_census.py counts their branches too)."""
+    rng = np.random.default_rng(2024)
+    vocab = [rng.integers(0, 256, 4, dtype=np.uint8).tobytes() for _ in range(12)]
+    tokens = np.frombuffer(b"".join(vocab[int(i)] for i in rng.integers(0, 12, 40000)), np.uint8)
+    head = rng.integers(0, 256, 7000, dtype=np.uint8)
+    far = np.concatenate([head[:2000], rng.integers(0, 256, 28000, dtype=np.uint8), head[:2768]])
+    skew = np.minimum(rng.geometric(0.02, 70000), 255).astype(np.uint8)
+    alt = np.tile(np.frombuffer(b"xyzw1234" * 3 + b"ABCD", np.uint8), 4000)
+    return [
+        tokens[:32768 * 3],                                                 # many 4-byte matches
+        np.concatenate([head, head[:500], rng.integers(0, 256, 9000, dtype=np.uint8), head]),  # long carries
+        far,                                                                # distances near 32 KiB
+        np.tile(np.frombuffer(b"0123456789abcdef" * 64, np.uint8), 70),     # long matches
+        skew,                                                               # all byte values, skewed
+        alt,                                                                # alternating offsets
+        np.concatenate([tokens[:5000], skew[:20000], tokens[5000:30000]]),
+    ]
+
+
+@pytest.mark.parametrize("name", ["zstd", "zstd-best-compression"])
+def test_zstd_table_carriers(name, gpu):
+    """Spans whose blocks (16 segments each) mix Raw_Blocks with compressed ones: the Huffman tree
+    and the FSE tables must ride on the first COMPRESSED block that uses them (a raw block 0, a
+    raw block between compressed ones, a literal-free block 0), later blocks reuse them (Treeless
+    literals, Repeat_Mode tables), and repeat offsets never reach back across a raw block.  Text
+    with literals above 128 takes the FSE-compressed weights description (RFC 8878 §4.2.1.2)."""
+    chunks = table_carrier_chunks()
     host = np.concatenate(chunks)
     lens = [c.size for c in chunks]
     offs = list(np.cumsum([0] + lens[:-1]))
@@ -278,22 +304,7 @@ def test_zstd_adversarial_spans(name, gpu):
     the longest carries (a block's literals before its first sequence), matches reaching 32 KiB
     back, long matches across whole segments, skewed literals over all 256 byte values, and
     sequences whose offsets alternate (repeat-offset candidates that must not be taken)."""
-    rng = np.random.default_rng(2024)
-    vocab = [rng.integers(0, 256, 4, dtype=np.uint8).tobytes() for _ in range(12)]
-    tokens = np.frombuffer(b"".join(vocab[int(i)] for i in rng.integers(0, 12, 40000)), np.uint8)
-    head = rng.integers(0, 256, 7000, dtype=np.uint8)
-    far = np.concatenate([head[:2000], rng.integers(0, 256, 28000, dtype=np.uint8), head[:2768]])
-    skew = np.minimum(rng.geometric(0.02, 70000), 255).astype(np.uint8)
-    alt = np.tile(np.frombuffer(b"xyzw1234" * 3 + b"ABCD", np.uint8), 4000)
-    parts = [
-        tokens[:32768 * 3],                                                 # many 4-byte matches
-        np.concatenate([head, head[:500], rng.integers(0, 256, 9000, dtype=np.uint8), head]),  # long carries
-        far,                                                                # distances near 32 KiB
-        np.tile(np.frombuffer(b"0123456789abcdef" * 64, np.uint8), 70),     # long matches
-        skew,                                                               # all byte values, skewed
-        alt,                                                                # alternating offsets
-        np.concatenate([tokens[:5000], skew[:20000], tokens[5000:30000]]),
-    ]
+    parts = adversarial_parts()
     host = np.concatenate(parts)
     lens = [p.size for p in parts]
     offs = [int(x) for x in np.cumsum([0] + lens[:-1])]

@@ -3,7 +3,9 @@ of tests/zstd_vectors.py (libzstd is the first) and the reader of every vector's
 Python over bytes, one symbol at a time; nothing here is shared with the code under test.
 
 decode(stream) -> (bytes, [Frame]) or raises Bad; walk(stream) -> [Frame] from the headers alone
-(no entropy decoding, so it is quick on the megabyte vectors).  The choices the library makes where
+(no entropy decoding, so it is quick on the megabyte vectors); decode(stream, detail=True) ->
+(bytes, [Frame], [[Detail]]): one Detail per block with everything the block's sections hold
+(tests/zstd_structure.py checks the span encoder's choices on them).  The choices the library makes where
 readers differ (kopia_amd/csrc/kcdc_zstd_format.h lists them) are made here too: a non-zero
 Dictionary_ID is refused, an offset may not pass the frame's own output or Window_Size, a block may
 not decode past Block_Maximum_Size."""
@@ -28,6 +30,21 @@ class Bad(Exception):
 
 Block = namedtuple("Block", "type size last lit_type streams size_format weights modes nseq reps decoded")
 Frame = namedtuple("Frame", "single fcs_bytes window checksum did_bytes blocks skippable")
+# One block in full (decode(detail=True)).  Every block: type (0 raw, 1 RLE, 2 compressed), size (the
+# header's Block_Size), at / out_len (its bytes in the frame's output).  A compressed block besides:
+#   lit_type, lits (the literal bytes), lit_hlen (header bytes), lit_comp (Compressed_Size; the
+#   section's bytes after the header), streams, jump (the three jump-table sizes, or None);
+#   weights (with the implied last one), maxbits (the longest code), tree_bytes (the description's
+#   bytes, header byte included), tree_kind ('direct' | 'fse'): None / 0 without a tree;
+#   fields: for LL, OF, ML a Field(mode, log, norm, rle, desc_bytes, desc): the accuracy log and counts
+#   of a Predefined or FSE_Compressed table, the symbol of an RLE one, None for what Repeat_Mode keeps;
+#   desc: the description's bytes (the RLE symbol's byte), desc_bytes their number;
+#   seqs: [(ll, ml, offset value, resolved offset)]; nseq_bytes (Number_of_Sequences), seq_hlen (that,
+#   the modes byte and the descriptions), bitstream (the bytes after them).
+Field = namedtuple("Field", "mode log norm rle desc_bytes desc")
+Detail = namedtuple("Detail", "type size at out_len lit_type lits lit_hlen lit_comp streams jump weights maxbits "
+                    "tree_bytes tree_kind fields seqs nseq_bytes seq_hlen bitstream",
+                    defaults=(None, b"", 0, 0, 0, None, None, 0, 0, None, (), (), 0, 0, 0))
 
 
 def need(cond, what):
@@ -245,10 +262,11 @@ class State:
         self.rep = [1, 4, 8]
 
 
-def decode_block(blk, st, out, frame_at, window, block_max, entropy=True):
-    """A compressed block: appends to out, returns its Block."""
+def decode_block(blk, st, out, frame_at, window, block_max, entropy=True, rec=None):
+    """A compressed block: appends to out, returns its Block (rec: a list that takes its Detail)."""
     t, sf, hlen, regen, comp, streams = lit_header(blk)
     weights = None
+    d = {"lit_type": t, "lit_hlen": hlen, "lit_comp": comp, "streams": streams}
     body = blk[hlen:hlen + comp]
     if t == 0:
         lits = body
@@ -258,6 +276,7 @@ def decode_block(blk, st, out, frame_at, window, block_max, entropy=True):
         if t == 2:
             w, log, used, weights = read_weights(body)
             st.huf = (huffman_table(w, log), log)
+            d.update(weights=w, maxbits=log, tree_bytes=used, tree_kind=weights)
             body = body[used:]
         need(st.huf is not None, "Treeless literals without a tree")
         lits = None
@@ -271,6 +290,7 @@ def decode_block(blk, st, out, frame_at, window, block_max, entropy=True):
                 need(l1 + l2 + l3 <= len(body) - 6, "jump table larger than its section")
                 seg = (regen + 3) // 4
                 need(3 * seg <= regen, "4 streams for too few literals")
+                d["jump"] = (l1, l2, l3)
                 at, lits = 6, b""
                 for k, ln in enumerate((l1, l2, l3, len(body) - 6 - l1 - l2 - l3)):
                     lits += huffman_stream(body[at:at + ln], table, log, seg if k < 3 else regen - 3 * seg)
@@ -279,24 +299,36 @@ def decode_block(blk, st, out, frame_at, window, block_max, entropy=True):
     nseq, h, modes = seq_header(sec)
     reps = set()
     start = len(out)
+    fields, seqs = [], []
+    d.update(lits=lits, fields=fields, seqs=seqs, nseq_bytes=h - (1 if nseq else 0), seq_hlen=h)
+
+    def done(b):
+        if rec is not None:
+            rec.append(Detail(2, len(blk), start - frame_at, len(out) - start, **d))
+        return b
     if nseq:
         need(regen + 3 * nseq <= block_max, "block decodes past its maximum")
         at = h
         for k in range(3):
             if modes[k] == 0:
                 st.tables[k] = (fse_table(*DEFAULTS[k]), DEFAULTS[k][1])
+                fields.append(Field(0, DEFAULTS[k][1], list(DEFAULTS[k][0]), None, 0, b""))
             elif modes[k] == 1:
                 need(len(sec) > at and sec[at] <= MAX_SYM[k], "RLE symbol beyond the table")
                 st.tables[k] = ([(sec[at], 0, 0)], 0)
+                fields.append(Field(1, 0, None, sec[at], 1, sec[at:at + 1]))
                 at += 1
             elif modes[k] == 2:
                 norm, log, used = read_fse(sec[at:], MAX_LOG[k], MAX_SYM[k])
                 st.tables[k] = (fse_table(norm, log), log)
+                fields.append(Field(2, log, norm, None, used, sec[at:at + used]))
                 at += used
             else:
                 need(st.tables[k] is not None, "Repeat_Mode without a table")
+                fields.append(Field(3, None, None, None, 0, b""))
+        d.update(seq_hlen=at, bitstream=len(sec) - at)
         if not entropy:
-            return Block(2, len(blk), 0, t, streams, sf, weights, modes, nseq, reps, None)
+            return done(Block(2, len(blk), 0, t, streams, sf, weights, modes, nseq, reps, None))
         b = Back(sec[at:])
         (lt, ll_log), (ot, of_log), (mt, ml_log) = st.tables
         ls, os_, ms = b.read(ll_log), b.read(of_log), b.read(ml_log)
@@ -330,6 +362,7 @@ def decode_block(blk, st, out, frame_at, window, block_max, entropy=True):
             need(off <= len(out) - frame_at, "offset beyond the bytes the frame has produced")
             need(off <= window, "offset beyond the window")
             need(len(out) - start + ml <= block_max, "block decodes past its maximum")
+            seqs.append((ll, ml, ofv, off))
             if off >= ml:
                 out += out[len(out) - off:len(out) - off + ml]
             else:
@@ -339,10 +372,10 @@ def decode_block(blk, st, out, frame_at, window, block_max, entropy=True):
         out += lits[lp:]
     else:
         if not entropy:
-            return Block(2, len(blk), 0, t, streams, sf, weights, modes, 0, reps, None)
+            return done(Block(2, len(blk), 0, t, streams, sf, weights, modes, 0, reps, None))
         out += lits
     need(len(out) - start <= block_max, "block decodes past its maximum")
-    return Block(2, len(blk), 0, t, streams, sf, weights, modes, nseq, reps, len(out) - start)
+    return done(Block(2, len(blk), 0, t, streams, sf, weights, modes, nseq, reps, len(out) - start))
 
 
 def xxh64(data):
@@ -379,10 +412,12 @@ def xxh64(data):
     return h ^ (h >> 32)
 
 
-def decode(stream, entropy=True):
-    """(decoded bytes, [Frame]).  entropy=False: the headers alone (bytes are not produced)."""
+def decode(stream, entropy=True, detail=False):
+    """(decoded bytes, [Frame]).  entropy=False: the headers alone (bytes are not produced).
+    detail=True: (decoded bytes, [Frame], [[Detail] per frame]), one Detail per block."""
     stream = bytes(stream)
     out, frames, pos, n = bytearray(), [], 0, len(stream)
+    details = []
     while pos < n:
         need(n - pos >= 4, "truncated magic")
         magic = int.from_bytes(stream[pos:pos + 4], "little")
@@ -393,6 +428,7 @@ def decode(stream, entropy=True):
             need(size <= n - pos - 4, "truncated skippable frame")
             pos += 4 + size
             frames.append(Frame(0, 0, 0, 0, 0, [], True))
+            details.append([])
             continue
         need(magic == 0xFD2FB528, "bad magic")
         need(n - pos >= 1, "truncated frame header")
@@ -419,6 +455,7 @@ def decode(stream, entropy=True):
             window = fcs
         block_max = min(window, BLOCK_MAX)
         st, blocks, frame_at = State(), [], len(out)
+        rec = []
         while True:
             need(n - pos >= 3, "truncated block header")
             bh = int.from_bytes(stream[pos:pos + 3], "little")
@@ -428,17 +465,19 @@ def decode(stream, entropy=True):
             need(size <= block_max, "block over Block_Maximum_Size")
             if btype == 0:
                 need(size <= n - pos, "truncated raw block")
+                rec.append(Detail(0, size, len(out) - frame_at, size))
                 out += stream[pos:pos + size]
                 pos += size
                 blocks.append(Block(0, size, last, None, 0, None, None, None, 0, set(), size))
             elif btype == 1:
                 need(n - pos >= 1, "truncated RLE block")
+                rec.append(Detail(1, size, len(out) - frame_at, size))
                 out += stream[pos:pos + 1] * size
                 pos += 1
                 blocks.append(Block(1, size, last, None, 0, None, None, None, 0, set(), size))
             else:
                 need(2 <= size <= n - pos and size < BLOCK_MAX, "truncated or oversized compressed block")
-                b = decode_block(stream[pos:pos + size], st, out, frame_at, window, block_max, entropy)
+                b = decode_block(stream[pos:pos + size], st, out, frame_at, window, block_max, entropy, rec)
                 blocks.append(b._replace(last=last))
                 pos += size
             if last:
@@ -451,6 +490,9 @@ def decode(stream, entropy=True):
                 need(int.from_bytes(stream[pos:pos + 4], "little") == xxh64(bytes(out[frame_at:])) & 0xFFFFFFFF, "checksum mismatch")
             pos += 4
         frames.append(Frame(single, fcs_bytes, window, checksum, did_bytes, blocks, False))
+        details.append(rec)
+    if detail:
+        return bytes(out), frames, details
     return bytes(out), frames
 
 

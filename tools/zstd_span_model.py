@@ -640,14 +640,18 @@ def encode_chunk_t(data, G):
         for g0 in range(0, len(segs), G):
             # a block's first sequence names its offset: the block before it may become a
             # Raw_Block, which leaves the decoder's repeat offsets where the last compressed one did
-            lits, seqs, carry, prev_off = [], [], 0, None
+            # (zstd_ov's rule: the previous distance again is offset value 1 with literals, and
+            # without them when the previous sequence had none either and the one before it
+            # had this distance too: repeat offset 2 then names it)
+            lits, seqs, carry, prev_off, prev2_off, prev_ll = [], [], 0, None, None, None
             for i in range(g0, min(g0 + G, len(segs))):
                 sq, tail = segs[i]
                 lits += seg_lits[i]
                 for k, (ll, ml, d) in enumerate(sq):
                     ll2 = ll + (carry if k == 0 else 0)
-                    seqs.append((ll2, ml, 1 if (ll2 > 0 and d == prev_off) else d + 3))
-                    prev_off = d
+                    rep = d == prev_off and (ll2 > 0 or (prev_ll == 0 and d == prev2_off))
+                    seqs.append((ll2, ml, 1 if rep else d + 3))
+                    prev_off, prev2_off, prev_ll = d, prev_off, ll2
                 carry = tail if sq else carry + len(seg_lits[i])
             blocks.append((lits, seqs, span[g0 * SEG:min(len(span), (g0 + G) * SEG)]))
         all_seqs = [q for _, sq, _ in blocks for q in sq]
