@@ -599,6 +599,78 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
                                   uint64_t* d_out_lens, int32_t* d_status, void* d_work, uint64_t work_bytes,
                                   void* hip_stream);
 
+/* ------------------------------------------------------------- packing
+ * What the content manager does with a new content between the cut and the pack blob
+ * (maybeCompressAndEncryptDataForPacking, repo/content/content_manager_lock_free.go:30-89, and the
+ * append of addToPackUnlocked, content_manager.go:257-353), for many chunks per call with no host
+ * round trip between the stages.  Per content, in order:
+ *   1. compress (if `compression` is set): out = BE32(header ID) || stream, kept iff
+ *      len(out) < len(chunk); otherwise the header ID is 0 and the original is used
+ *      (kcdc_compress_chunks_device);
+ *   2. seal with `encryption`, IV = the content ID, nonce from the caller
+ *      (kcdc_encrypt_chunks_device);
+ *   3. wrap with `ecc` if set (kcdc_ecc_encode_chunks_device);
+ *   4. append to the pack: PackOffset = the pack's length, PackedLength = the stored length; a pack
+ *      whose length is >= max_pack_size after the append is closed and the next content opens a new
+ *      one, whose length starts at pack_lead (content_manager.go:314-334).
+ * The host keeps the dedup decision, blob IDs, the preamble's bytes, the postamble, the index and
+ * the split by pack prefix: one call packs the contents of one prefix.
+ * kcdc_pack_params: max_pack_size 1..2^30; pack_lead: bytes left free at the head of every new pack
+ *   (the host fills them); open_fill: 0, or the length (< max_pack_size) of an open pack that pack 0
+ *   of this call continues; max_total_bytes (<= 2^40): the caller's bound on the sum of the packed
+ *   chunks' lengths, which sizes the workspace.
+ * kcdc_pack_bounds: for nchunks chunks under these parameters, the bytes of d_pack, the rows of
+ *   d_packs and the bytes of d_work that no call can exceed.
+ * kcdc_pack_chunks_device: chunk i = [d_offsets[i], +d_lens[i]) of d_data (any alignment);
+ *   d_keep[i] == 0 leaves chunk i out (NULL: all are packed); d_ids / d_nonces as
+ *   kcdc_encrypt_chunks_device's d_ivs / d_nonces.
+ *   Layout of d_pack: pack 0 starts at 0 and pack k+1 at pack k's end rounded up to 256; the bytes of
+ *   pack k from pack offset x on are at d_packs[k].start + x, x >= pack_lead (open_fill for pack 0
+ *   when it is non-zero).  The lead bytes and the gaps are never written.  A pack exists only if a
+ *   content went into it; only the last may be open (length < max_pack_size).
+ *   d_entries[i].status: 0 packed; KCDC_PACK_SKIPPED (d_keep[i] == 0) and KCDC_EFBIG (longer than
+ *   the seal's limit, 2^30 - 64) take no room.  Decided on the device for the whole call, with
+ *   d_totals = {0, 0} and no byte of d_pack written: KCDC_ENOMEM in every entry if the packed
+ *   lengths sum to more than max_total_bytes, KCDC_EOVERFLOW if the packs do not fit pack_cap or
+ *   packs_cap (neither arises with buffers sized by kcdc_pack_bounds from a true max_total_bytes).
+ *   d_totals[0]: packs; d_totals[1]: bytes of d_pack used (the last pack's end).  Rows of d_packs
+ *   from d_totals[0] on are not written, except that a KCDC_EOVERFLOW call may leave the rows it
+ *   placed before it refused (never more than packs_cap).
+ *   d_work: 256-byte aligned, work_bytes >= kcdc_pack_bounds'.  Asynchronous on hip_stream: no host
+ *   synchronisation, allocation or copy; every array is device memory and must stay allocated until
+ *   the work finishes.  nchunks == 0 only zeroes d_totals.
+ *   Returns KCDC_ENOENT (unknown name), KCDC_EINVAL (bad parameter, null argument, misaligned or
+ *   short workspace) or KCDC_ENODEV before anything is launched. */
+#define KCDC_PACK_SKIPPED 1
+typedef struct kcdc_pack_params {
+    const char* compression;      /* a kcdc_compression_algorithms name, or NULL: NoCompression */
+    const char* encryption;       /* a kcdc_encryption_algorithms name */
+    const uint8_t* secret;
+    uint32_t secret_len;
+    const char* ecc;              /* NULL: none, else a kcdc_ecc_algorithms name */
+    int32_t ecc_overhead_percent, ecc_max_shard_size;
+    uint64_t max_pack_size;
+    uint32_t pack_lead;
+    uint32_t open_fill;
+    uint64_t max_total_bytes;
+} kcdc_pack_params;
+typedef struct kcdc_pack_entry { /* 24 bytes, one per chunk: the Info fields the device decides */
+    uint32_t pack, pack_offset, packed_length, original_length, header_id;
+    int32_t status;
+} kcdc_pack_entry;
+typedef struct kcdc_pack_info { /* 24 bytes, one per pack */
+    uint64_t start, length;     /* place in d_pack; the pack's length, lead / open_fill included */
+    uint32_t first, count;      /* its contents are the count packed chunks from chunk index first on */
+} kcdc_pack_info;
+int kcdc_pack_bounds(const kcdc_pack_params* params, uint32_t nchunks, uint64_t* pack_bytes, uint32_t* max_packs,
+                     uint64_t* work_bytes);
+int kcdc_pack_chunks_device(const kcdc_pack_params* params, const uint8_t* d_data, const uint64_t* d_offsets,
+                            const uint64_t* d_lens, const uint8_t* d_keep, uint32_t nchunks, const uint8_t* d_ids,
+                            uint32_t id_len, uint32_t id_stride, const uint8_t* d_nonces, uint8_t* d_pack,
+                            uint64_t pack_cap, kcdc_pack_entry* d_entries, kcdc_pack_info* d_packs,
+                            uint32_t packs_cap, uint64_t* d_totals, void* d_work, uint64_t work_bytes,
+                            void* hip_stream);
+
 /* ------------------------------------------------------------- testing
  * Hooks for the library's own tests (not part of the splitter surface).
  * kcdc_test_set: process-wide knobs read by every later batch launch.

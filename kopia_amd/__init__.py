@@ -13,6 +13,8 @@ kernels in ``libkcdc.so``; see DESIGN.md.  Public Python surface:
   ``Encryptor``, ``SupportedAlgorithms``, ``derive_key``).
 * :mod:`kopia_amd.compression` — ``deflate-*``, ``gzip*`` and ``pgzip*`` compression of many
   chunks with the content manager's keep-or-drop rule (``repo/compression``; ``Compressor``).
+* :mod:`kopia_amd.packing` — compress, seal, ECC and placement in packs in one device call
+  (``repo/content``: ``maybeCompressAndEncryptDataForPacking``, ``addToPackUnlocked``; ``Packer``).
 """
 from . import _lib  # noqa: F401
 from . import compression, encryption, hashing  # noqa: F401

@@ -28,6 +28,7 @@ KCDC_EINVAL = -22
 KCDC_EOVERFLOW = -75
 KCDC_EFBIG = -27
 KCDC_EBADMSG = -74
+KCDC_PACK_SKIPPED = 1  # status of a chunk that d_keep left out of a pack call
 KCDC_ECC_DAMAGED = 1  # status of a decoded chunk with failed shards, before the repair
 
 KIND_FIXED, KIND_BUZHASH, KIND_RABINKARP = 0, 1, 2
@@ -57,6 +58,13 @@ class KcdcError(RuntimeError):
 class AlgoInfo(C.Structure):
     _fields_ = [("kind", C.c_int32), ("pooled", C.c_int32), ("avg", C.c_uint64), ("min_size", C.c_uint64),
                 ("max_size", C.c_uint64), ("mask", C.c_uint64)]
+
+
+class PackParams(C.Structure):  # kcdc_pack_params
+    _fields_ = [("compression", C.c_char_p), ("encryption", C.c_char_p), ("secret", C.c_char_p),
+                ("secret_len", C.c_uint32), ("ecc", C.c_char_p), ("ecc_overhead_percent", C.c_int32),
+                ("ecc_max_shard_size", C.c_int32), ("max_pack_size", C.c_uint64), ("pack_lead", C.c_uint32),
+                ("open_fill", C.c_uint32), ("max_total_bytes", C.c_uint64)]
 
 
 class EccInfo(C.Structure):
@@ -158,6 +166,11 @@ _SIGS = {
                                                 _P, _P, C.c_uint64, _P]),
     "kcdc_ecc_repair_chunks_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P,
                                                 _P, _P, C.c_uint64, _P]),
+    "kcdc_pack_bounds": (C.c_int, [C.POINTER(PackParams), C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint64)]),
+    "kcdc_pack_chunks_device": (C.c_int, [C.POINTER(PackParams), _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32,
+                                          C.c_uint32, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint64,
+                                          _P]),
 }
 
 

@@ -16,6 +16,7 @@
 #include "../../include/kcdc.h"
 #include "kcdc_hip.h"
 #include "kcdc_internal.h"
+#include "kcdc_pack_format.h"
 
 namespace kcdc {
 const char* last_error_cstr();
@@ -1116,4 +1117,78 @@ extern "C" int kcdc_zstd_decode_chunks_device(const char* algorithm, const uint8
         return set_error(KCDC_EINVAL, "null argument");
     return launch_zstd_decode(header_id, d_comp, d_offsets, d_comp_lens, nchunks, d_out, d_out_offsets, d_out_caps,
                               d_out_lens, d_status, d_work, work_bytes, hip_stream);
+}
+
+// ======================================================= packing
+// Parameter checks and bounds of kcdc_pack_chunks_device; the kernels are in kcdc_pack.hip and every
+// decision in kcdc_pack_format.h.
+static int pack_run(const kcdc_pack_params* p, PackRun* r) {
+    if (!p) return set_error(KCDC_EINVAL, "null argument");
+    *r = PackRun{};
+    if (p->compression && kcdc_compression_header_id(p->compression) < 0) return KCDC_ENOENT;
+    if (kcdc_encryption_overhead(p->encryption) < 0) return KCDC_ENOENT;
+    if (p->ecc) {
+        if (int rc = ecc_lookup(p->ecc, p->ecc_overhead_percent, p->ecc_max_shard_size, &r->rule.ep)) return rc;
+        r->rule.ecc = 1;
+    }
+    if (!p->secret || p->secret_len == 0 || p->secret_len > 64)
+        return set_error(KCDC_EINVAL, "secret must be 1..64 bytes (the HKDF-derived key is 32)");
+    if (p->max_pack_size == 0 || p->max_pack_size > packfmt::kMaxPackSize)
+        return set_error(KCDC_EINVAL, "max_pack_size must be 1..2^30");
+    if (p->open_fill >= p->max_pack_size)
+        return set_error(KCDC_EINVAL, "open_fill must be below max_pack_size (a pack that long is closed)");
+    if (p->max_total_bytes > packfmt::kMaxTotalBytes) return set_error(KCDC_EINVAL, "max_total_bytes must be <= 2^40");
+    r->rule.max_pack_size = p->max_pack_size;
+    r->rule.lead = p->pack_lead;
+    r->rule.open_fill = p->open_fill;
+    r->compression = p->compression;
+    r->encryption = p->encryption;
+    r->ecc = p->ecc;
+    r->secret = p->secret;
+    r->secret_len = p->secret_len;
+    r->ecc_overhead = p->ecc_overhead_percent;
+    r->ecc_max_shard = p->ecc_max_shard_size;
+    r->max_total = p->max_total_bytes;
+    return KCDC_OK;
+}
+
+extern "C" int kcdc_pack_bounds(const kcdc_pack_params* params, uint32_t nchunks, uint64_t* pack_bytes,
+                                uint32_t* max_packs, uint64_t* work_bytes) {
+    PackRun r{};
+    if (int rc = pack_run(params, &r)) return rc;
+    const uint64_t stored = packfmt::stored_bound(r.rule, r.max_total, nchunks);
+    const uint64_t packs = packfmt::packs_bound(r.rule, stored, nchunks);
+    if (pack_bytes) *pack_bytes = packfmt::pack_bytes_bound(r.rule, stored, packs);
+    if (max_packs) *max_packs = static_cast<uint32_t>(packs);
+    if (work_bytes) *work_bytes = pack_workspace_size(r, nchunks);
+    return KCDC_OK;
+}
+
+extern "C" int kcdc_pack_chunks_device(const kcdc_pack_params* params, const uint8_t* d_data, const uint64_t* d_offsets,
+                                       const uint64_t* d_lens, const uint8_t* d_keep, uint32_t nchunks,
+                                       const uint8_t* d_ids, uint32_t id_len, uint32_t id_stride,
+                                       const uint8_t* d_nonces, uint8_t* d_pack, uint64_t pack_cap,
+                                       kcdc_pack_entry* d_entries, kcdc_pack_info* d_packs, uint32_t packs_cap,
+                                       uint64_t* d_totals, void* d_work, uint64_t work_bytes, void* hip_stream) {
+    PackRun r{};
+    if (int rc = pack_run(params, &r)) return rc;
+    if (id_len == 0 || id_len > 64) return set_error(KCDC_EINVAL, "content ID (iv) must be 1..64 bytes");
+    if (id_stride < id_len && nchunks > 1) return set_error(KCDC_EINVAL, "id_stride must be >= id_len");
+    if (!d_totals) return set_error(KCDC_EINVAL, "null argument");
+    if (nchunks != 0) {
+        if (!d_data || !d_offsets || !d_lens || !d_ids || !d_nonces || !d_pack || !d_entries || !d_packs || !d_work)
+            return set_error(KCDC_EINVAL, "null argument");
+        if (reinterpret_cast<uintptr_t>(d_work) % 256u) return set_error(KCDC_EINVAL, "d_work must be 256-byte aligned");
+        if (work_bytes < pack_workspace_size(r, nchunks))
+            return set_error(KCDC_EINVAL, "workspace too small (kcdc_pack_bounds)");
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (int rc = check_device(dev)) return rc;
+    if (nchunks == 0) {
+        HIP_TRY(hipMemsetAsync(d_totals, 0, 16, static_cast<hipStream_t>(hip_stream)), "hipMemsetAsync(d_totals)");
+        return KCDC_OK;
+    }
+    return launch_pack(r, d_data, d_offsets, d_lens, d_keep, nchunks, d_ids, id_len, id_stride, d_nonces, d_pack,
+                       pack_cap, d_entries, d_packs, packs_cap, d_totals, d_work, work_bytes, hip_stream);
 }

@@ -42,6 +42,7 @@
 #include <string>
 
 #include "kcdc_internal.h"
+#include "kcdc_pack_format.h"
 #include "kcdc_wave.h"
 
 namespace kcdc {
@@ -2889,7 +2890,8 @@ extern "C" int64_t kcdc_compression_header_id(const char* name) {
 }
 
 extern "C" uint64_t kcdc_compress_bound(uint64_t len) {  // + 18: a gzip member's header and trailer (>= zstd's 13 + 3)
-    return 24u + len + 5u * ((len + compdev::kSeg - 1) / compdev::kSeg);
+    static_assert(compdev::kSeg == 512, "packfmt::compress_bound counts 512-byte segments");
+    return packfmt::compress_bound(len);  // shared with the pack plan, which lays out compress slots on the device
 }
 
 extern "C" uint64_t kcdc_compress_workspace_size(uint64_t total_bytes, uint32_t nchunks) {
