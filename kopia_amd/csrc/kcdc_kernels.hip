@@ -431,7 +431,7 @@ int launch_split_batch(const Algo& algo, const SplitArgs& s, int device, void* s
         a.ring_mask = static_cast<uint32_t>(p.ring - 1);
 
 #if KCDC_TRACE
-        if (trace_reserve(std::max<uint64_t>(s.nstreams, 3ull * p.grid * p.wg_waves)) != 0) return set_error(-12, "trace buffer");
+        if (trace_reserve(std::max<uint64_t>(s.nstreams, 5ull * p.grid * p.wg_waves)) != 0) return set_error(-12, "trace buffer");
         a.trace = g_trace;
 #endif
         // header + ring zeroed per launch (the ring is also left empty by every finished launch)

@@ -41,9 +41,16 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
     uint8_t* wl = smwarm.b[wave];
     const uint32_t sl32 = lds_addr(sl), wl32 = lds_addr(wl);
 #if KCDC_TRACE  // per wave at trace[8 * global wave]: start, end, ticks in blocking takes, the last take's
-                // start, help tiles, their ticks, the end of the wave's last own tile, own tiles
+                // start, help tiles, their ticks, the end of the wave's last own tile, own tiles; and the
+                // hand-off sums at trace[8 * waves + 5 * global wave], each {count << 32 | ticks}: tile
+                // start to the end of the tile-top wait in switching own tiles (it covers the ticket add)
+                // and in the other own tiles (prefetched tiles that publish nothing only; a wait timed
+                // by itself misses the add, whose result the compiler waits for a few instructions
+                // earlier), adopt prefetch to the end of the adopted tile's top wait, one-step own tiles (whole tile), blocking takes of a
+                // fresh ticket after the wave's first stream that returned work (those after a cut)
     const uint32_t gw = blockIdx.x * kDmaWaves + wave;
     uint64_t tr_block = 0, tr_last = 0, tr_help = 0, tr_help_t = 0, tr_own_end = 0, tr_own = 0;
+    uint64_t tr_wsw = 0, tr_wns = 0, tr_adopt = 0, tr_one = 0, tr_cut = 0, tr_pf = 0;
     if (lane == 0) a.trace[8 * gw] = __builtin_amdgcn_s_memrealtime();
 #define KCDC_PRET                                                                 \
     do {                                                                          \
@@ -55,6 +62,12 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             a.trace[8 * gw + 5] = tr_help_t;                                      \
             a.trace[8 * gw + 6] = tr_own_end;                                     \
             a.trace[8 * gw + 7] = tr_own;                                         \
+            uint64_t* const tr_x = a.trace + 8ull * gridDim.x * kDmaWaves + 5ull * gw;  \
+            tr_x[0] = tr_wsw;                                                     \
+            tr_x[1] = tr_wns;                                                     \
+            tr_x[2] = tr_adopt;                                                   \
+            tr_x[3] = tr_one;                                                     \
+            tr_x[4] = tr_cut;                                                     \
         }                                                                         \
         return;                                                                   \
     } while (0)
@@ -70,7 +83,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
     Visit v;
     PStream& cur = v.cur;
     // The buzhash visit quantum (pipe_quantum_tiles) for visit_take and visit_adopt.
-    const auto quantum = [&](int64_t backlog) { return pipe_quantum_tiles(backlog, a.lane_cap); };
+    const auto quantum = [&](int64_t backlog) { return pipe_quantum_tiles(backlog, a.lane_cap, a.max_size - a.min_size); };
     visit_first_ticket<kDmaWaves>(a, lane, wave, v);
     for (;;) {
         visit_diag_take(a, lane, v);
@@ -79,10 +92,13 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
 #if KCDC_TRACE
             const uint64_t tb0 = __builtin_amdgcn_s_memrealtime();
             tr_last = tb0;
+            const bool tr_fresh = v.take_t == 0xFFFFFFFFu && tr_own != 0;
 #endif
             const bool taken = visit_take<kDmaWaves>(a, lane, me, v, quantum);
 #if KCDC_TRACE
-            tr_block += __builtin_amdgcn_s_memrealtime() - tb0;
+            const uint64_t tr_dt = __builtin_amdgcn_s_memrealtime() - tb0;
+            tr_block += tr_dt;
+            if (taken && tr_fresh) tr_cut += (1ull << 32) + tr_dt;
 #endif
             if (!taken) KCDC_PRET;
         }
@@ -94,6 +110,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
         const uint64_t tr_t0 = __builtin_amdgcn_s_memrealtime();
         if (is_help) tr_help++;
         else tr_own++;
+        const bool tr_pre = v.issued && !(v.hs & kHsNeedPub);  // prefetched, and publishes nothing
 #endif
         int64_t lo, hi;
         pregion(a, cur, lo, hi);
@@ -116,12 +133,26 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             uint32_t w16[16];
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(ht_lo), "+v"(ht_hi)::"memory");
+#if KCDC_TRACE
+            const uint64_t tr_w1 = __builtin_amdgcn_s_memrealtime();
+            if (!is_help) {
+                if (tr_pre && switching) tr_wsw += (1ull << 32) + (tr_w1 - tr_t0);
+                else if (tr_pre) tr_wns += (1ull << 32) + (tr_w1 - tr_t0);
+                if (tr_pf) tr_adopt += (1ull << 32) + (tr_w1 - tr_pf);
+            }
+            tr_pf = 0;
+#endif
             read_piece(wl, lane, 1, cur.off0, w16);  // (the piece before coordinate 0 reads as zeros)
             hash.clear();
             hash.template block<kWarm>(w16);
         }
         tile.set_ticket(ht_lo, ht_hi);
-        int32_t found = -1;  // offset from ct of this lane's first candidate
+        // Offset from ct of this lane's first candidate.  A region's tile 0 that starts at lo + 1
+        // (region_ct0) tests lo here: lane 0's state after the warm-up is the hash at ct - 1, and
+        // lo precedes every position of the tile.  (A help task's lo is its ct.)
+        constexpr int32_t kNoCand = INT32_MIN;
+        int32_t found = kNoCand;
+        if (ct == lo + 1 && lane == 0 && (hash.h & hash.mask) == 0) found = -1;
         const int poll_step = g.nb > 1 ? g.nb / 2 : 0;
         // The owner's claim on tile htile + 1: an atomic add on its slot's bottom in step 0 (no
         // return value: nothing stays live across the hashing), the word read back by an sc1
@@ -148,7 +179,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             if (n + 1 < g.nb) {
                 dma_step128(g.ld, g.ld.tb, sl32, ct, g.L, n + 1, lane);
             } else if (!switching && !last_of_region && tile.claim_known && (!claim_next || tile.claim_ok) &&
-                       __ballot(found >= 0) == 0) {
+                       __ballot(found != kNoCand) == 0) {
                 // (a candidate in an earlier step means the region's cut is in this tile: the
                 // next tile would be a stale prefetch, 12 KiB of HBM traffic per chunk wasted --
                 // 9 % of R at 128K, where chunks span ~4 tiles)
@@ -162,7 +193,7 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t m = hash.template step128<TOP>(dw, 0u);
             __builtin_amdgcn_sched_barrier(0);
-            if (m <= lim && found < 0 && cl <= hi_rel) {  // rare: exact re-run from global memory
+            if (m <= lim && found == kNoCand && cl <= hi_rel) {  // rare: exact re-run from global memory
                 const int64_t c = ct + cl;
                 uint32_t prv[16], cur32[32];
                 g.ld.load(c - 64, prv);
@@ -186,10 +217,13 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
                 tile.claim_decode(v, qht_value(static_cast<uint32_t>(raw), static_cast<uint32_t>(raw >> 32)));
             }
         }
-        const uint64_t hit = __ballot(found >= 0);
+        const uint64_t hit = __ballot(found != kNoCand);
 #if KCDC_TRACE
         if (is_help) tr_help_t += __builtin_amdgcn_s_memrealtime() - tr_t0;
-        else tr_own_end = __builtin_amdgcn_s_memrealtime();
+        else {
+            tr_own_end = __builtin_amdgcn_s_memrealtime();
+            if (g.nb == 1) tr_one += (1ull << 32) + (tr_own_end - tr_t0);
+        }
 #endif
         // the tile's first candidate (coordinate), or -1
         const int64_t f = hit ? ct + __builtin_amdgcn_readfirstlane(__shfl(found, __builtin_ctzll(hit))) : -1;
@@ -198,12 +232,15 @@ __global__ __launch_bounds__(kDmaWaves * kWave, kDmaWaves / 4) void split_batch_
         // drained it); prefetch its first tile now, under this tile's bookkeeping
         const auto prefetch = [&](PStream& nx) {
             if (nx.ct < 0 && nx.s < nx.n && nx.s + static_cast<int64_t>(a.min_size) - 1 < nx.n)
-                nx.ct = (nx.s + static_cast<int64_t>(a.min_size) - 1 + nx.off0) & ~int64_t(127);
+                nx.ct = region_ct0(a, nx.s, nx.n, nx.off0, /*line_start=*/true);
             if (nx.ct < 0) return false;
             int64_t nlo, nhi;
             pregion(a, nx, nlo, nhi);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // entry read before the slot refill
             ptile_issue(nx, nhi, wl32, sl32, lane, a.lane_cap);
+#if KCDC_TRACE
+            tr_pf = __builtin_amdgcn_s_memrealtime();
+#endif
             return true;
         };
         if (!visit_adopt(a, lane, v, wl, switching, switching ? tile.tk : 0xFFFFFFFFu, tile.nbacklog, quantum, prefetch)) KCDC_PRET;

@@ -67,10 +67,19 @@ constexpr uint32_t kStealSpins = 256;                            // ~0.5 ms of p
 //  * next tile of the same region: known in advance (the owner's claim on it, below);
 //  * next stream (quantum spent, or the region's last tile with no further region): the
 //    next ticket is taken by an atomic at the START of that tile and its ring entry
-//    (progress + stream parameters, 7 tagged 16-byte sc1 granules) loaded mid-tile, so
-//    both global round trips (~5 us each under full HBM load) hide under the hashing.
-// Only a candidate that ends a region early (the next region is not known before the
-// tile ends) and the first tile of the launch expose a DMA latency.
+//    (progress + stream parameters, 7 tagged 16-byte sc1 granules) loaded mid-tile.
+// What a stream switch hides and what it does not (buzhash kernel):
+//  * hidden under the hashing: the entry DMA, in a tile of three or more steps;
+//  * exposed: the ticket add, waited for at the top of the switching tile together with
+//    the tile's fills (~0.7 us there, traced: DESIGN.md §2.1); the adopted stream's first fill, issued after the
+//    tile (visit_adopt's prefetch) behind the requeue write and the help close; in a one-
+//    or two-step tile the entry DMA too; and a candidate that ends the stream: the next
+//    ticket is then taken by the blocking take (atomic, entry load, fill: three round
+//    trips in a row).
+// A candidate that ends a region early (the next region is not known before the tile ends)
+// and the first tile of the launch expose a DMA latency too.
+// A region whose lo is the last byte of a 128-byte line starts its grid at lo + 1
+// (region_ct0): regions of whole tiles end without a one-step tile.
 //
 // Intra-region help (round 4).  At the end of a batch -- and in any launch with fewer streams
 // than waves (a writer round, a handful of files) -- waves wait with nothing to scan while each
@@ -143,9 +152,29 @@ __device__ __forceinline__ void emit_cut(const BatchArgs& a, PStream& st, int la
     st.cnt++;
 }
 
+// Tile 0 of the region [lo, hi] of the chunk starting at s (lo = s + min - 1 + off0, coordinates).
+// Tiles start on 128-byte lines, so tile 0 is the line holding lo.  line_start (the buzhash batch
+// kernel): when lo is the LAST byte of its line, tile 0 starts at lo + 1 instead -- lane 0's state
+// after the warm-up of that tile is the hash at lo, which the kernel tests there.  The old grid
+// spent a whole tile position on that one byte: with min and max - min multiples of the tile, a
+// region without a candidate took a one-step tile more: a stream switch with nothing to hide its
+// round trips under (7.8 us a tile in the trace of DESIGN.md §2.1; next to no fetch, its other
+// lanes lie past the stream's end and are clipped).  A one-byte region (lo == hi) keeps the line rule.
+// Only an owner's tile 0 can start at lo + 1: helpers claim tiles >= 1 (help_publish sets bottom
+// = 1, help_find claims top - 1 >= bottom), windows and pending tiles re-start at tile >= 1, and
+// resume_ct's tiles hold a position > lo.
+__device__ __forceinline__ int64_t region_ct0(const BatchArgs& a, int64_t s, int64_t n, int64_t off0, bool line_start) {
+    const int64_t lo = s + static_cast<int64_t>(a.min_size) - 1 + off0;
+    if (line_start && (lo & 127) == 127) {
+        const int64_t mx = s + static_cast<int64_t>(a.max_size) - 1;
+        if (lo < (mx < n - 1 ? mx : n - 1) + off0) return lo + 1;
+    }
+    return lo & ~int64_t(127);
+}
+
 // Set up the next region to scan (chunks whose test range starts past the end are cut
 // at once); returns false when the stream is finished (all cuts emitted).
-__device__ __forceinline__ bool pstream_region(const BatchArgs& a, PStream& st, int lane) {
+__device__ __forceinline__ bool pstream_region(const BatchArgs& a, PStream& st, int lane, bool line_start = false) {
     while (st.ct < 0) {
         if (st.s >= st.n) return false;
         const int64_t pf = st.s + static_cast<int64_t>(a.min_size) - 1;
@@ -154,7 +183,7 @@ __device__ __forceinline__ bool pstream_region(const BatchArgs& a, PStream& st, 
             st.s = st.n;
             return false;
         }
-        st.ct = (pf + st.off0) & ~int64_t(127);
+        st.ct = region_ct0(a, st.s, st.n, st.off0, line_start);
     }
     return true;
 }
@@ -719,12 +748,23 @@ __device__ __forceinline__ void ptile_issue(const PStream& st, int64_t hi, uint3
 // run to completion; otherwise 768 KiB (short tail quanta measured no gain, and helpers now
 // split the tail's regions).
 __device__ __forceinline__ int64_t pipe_quantum(int64_t backlog, int64_t q = kPipeYield) { return backlog <= 0 ? kNoYield : q; }
-// The buzhash kernel's quantum in tiles: 6 full tiles, at least 512 KiB.  4M and larger averages
-// keep 6 x 128 KiB = 768 KiB (512 KiB there: 1.334 vs 1.286 ms); 128K and 256K get 512 KiB.  Against
-// the constant 768 KiB in one process (profiles/r04/third/ab_quantum_tiles_*.log): 128K 3.415 vs
-// 3.639 ms, 256K 2.697 vs 2.843, 4M 1.296 vs 1.309; all bit-exact.
-__device__ __forceinline__ int64_t pipe_quantum_tiles(int64_t backlog, uint32_t lane_cap) {
-    constexpr int64_t kTiles = 6, kMax = kTiles * kWave * 2048;  // (2 KiB lanes: 768 KiB)
+// The buzhash kernel's quantum in tiles, at least 512 KiB: the K tiles of a whole region
+// (region_bytes = max - min) in equal visits of at most 8 tiles, so no region ends in a short
+// visit that pays a hand-off for a few tiles.  512K and 1M (K = 6, 12) keep round 4's 6 tiles =
+// 768 KiB; 2M and larger averages (K = 24, 48, ..) get 8 x 128 KiB = 1 MiB; 128K and 256K get
+// 512 KiB.  Round 4 chose 6 tiles against the constant 768 KiB in one process
+// (profiles/r04/third/ab_quantum_tiles_*.log): 128K 3.415 vs 3.639 ms, 256K 2.697 vs 2.843, 4M
+// 1.296 vs 1.309 (512 KiB at 4M: 1.334 vs 1.286 ms); all bit-exact.  Round 7, 8 tiles against 6
+// (profiles/r07/handoff/): config 2 -1.1..-2.3 %, where region_ct0's line start makes a region
+// without a candidate 16 whole tiles (two visits instead of 6 + 6 + 4); 2M within the noise; 1M
+// (8 + 4) +5.5 %, hence the equal visits.
+__device__ __forceinline__ int64_t pipe_quantum_tiles(int64_t backlog, uint32_t lane_cap, uint64_t region_bytes) {
+    constexpr uint32_t kMostTiles = 8;
+    const uint32_t T = static_cast<uint32_t>(kWave) * lane_cap;
+    const uint32_t K = static_cast<uint32_t>((region_bytes + T - 1) / T);
+    const uint32_t visits = (K + kMostTiles - 1) / kMostTiles;
+    const int64_t kTiles = visits ? (K + visits - 1) / visits : kMostTiles;
+    const int64_t kMax = kTiles * kWave * 2048;  // (lanes above 2 KiB: as with 2 KiB lanes)
     const int64_t q = kTiles * kWave * static_cast<int64_t>(lane_cap);
     return pipe_quantum(backlog, q < (512 << 10) ? (512 << 10) : q > kMax ? kMax : q);
 }

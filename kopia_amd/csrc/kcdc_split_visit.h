@@ -22,6 +22,8 @@ namespace dev {
 // follows a tile's scan (help post, cut, requeue, the next stream).  The kernels keep the feed,
 // the hash, the candidate checks and the steps at which the atomics and DMAs are issued.  All of
 // it is wave-uniform and inlined at one site per kernel (presolve and try_steal are large).
+// Regions are set up by region_ct0's line-start rule: the one user of these functions, the buzhash
+// kernel, tests lo on the warm state of a tile that starts at lo + 1.
 constexpr uint32_t kHsPub = 1u << 16;     // the current region is published (claims are on)
 constexpr uint32_t kHsNeedPub = 1u << 17; // the region at cur.ct is new to this wave
 constexpr uint32_t kHsHelped = 1u << 18;  // the last claim saw helpers on the region: no yield
@@ -139,7 +141,7 @@ __device__ __forceinline__ bool visit_take(const BatchArgs& a, int lane, uint32_
         uniformize(cur);
         if (!pcheck(a, lane, cur, held, 1)) return false;
         v.budget = quantum(backlog);
-        if (pstream_region(a, cur, lane)) return true;
+        if (pstream_region(a, cur, lane, /*line_start=*/true)) return true;
         if (lane == 0) {  // nothing left to scan
             a.counts[cur.sid] = cur.cnt;
             add_agent(a.queue + kQDone, 1u);
@@ -285,7 +287,7 @@ __device__ __forceinline__ bool visit_resolve(const BatchArgs& a, int lane, uint
         if (v.hs & kHsPub) help_close(a, lane, me, v.hep);
         v.hs = kHsNeedPub;
     }
-    const bool live = pstream_region(a, cur, lane);
+    const bool live = pstream_region(a, cur, lane, /*line_start=*/true);
     if (!live && lane == 0) {
         a.counts[cur.sid] = cur.cnt;
         add_agent(a.queue + kQDone, 1u);
@@ -329,7 +331,7 @@ __device__ __forceinline__ bool visit_adopt(const BatchArgs& a, int lane, Visit&
             v.issued = prefetch(nx);
             v.cur = nx;
             v.budget = quantum(nbacklog);
-            if (pstream_region(a, v.cur, lane)) return true;
+            if (pstream_region(a, v.cur, lane, /*line_start=*/true)) return true;
             if (lane == 0) {  // nothing left to scan in it
                 a.counts[v.cur.sid] = v.cur.cnt;
                 add_agent(a.queue + kQDone, 1u);
