@@ -5,11 +5,11 @@ ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-function
 CSRC := kopia_amd/csrc
 OBJ := build/obj
-SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_inflate.hip $(CSRC)/kcdc_zstd.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_pack.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
+SRCS := $(CSRC)/kcdc_kernels.hip $(CSRC)/kcdc_hash.hip $(CSRC)/kcdc_crypt.hip $(CSRC)/kcdc_compress.hip $(CSRC)/kcdc_decompress.hip $(CSRC)/kcdc_inflate.hip $(CSRC)/kcdc_zstd.hip $(CSRC)/kcdc_ecc.hip $(CSRC)/kcdc_pack.hip $(CSRC)/kcdc_dedup.hip $(CSRC)/kcdc_api.cpp $(CSRC)/kcdc_writer.cpp $(CSRC)/kcdc_tables.cpp $(CSRC)/kcdc_registry.cpp
 OBJS := $(patsubst $(CSRC)/%,$(OBJ)/%.o,$(SRCS))
 LIB := kopia_amd/libkcdc.so
 
-all: $(LIB) oracle build/writer_bench build/s2_decode_host build/inflate_host build/zstd_decode_host build/pack_plan_host
+all: $(LIB) oracle build/writer_bench build/s2_decode_host build/inflate_host build/zstd_decode_host build/pack_plan_host build/dedup_host
 
 # every object depends on every header of the sources' directory: a header edit rebuilds
 HDRS := $(wildcard $(CSRC)/*.h) include/kcdc.h
@@ -91,6 +91,13 @@ build/zstd_decode_host: tools/zstd_decode_host.cpp $(CSRC)/kcdc_zstd_format.h
 # The pack plan's decisions (stored sizes, placement, bounds) on the CPU under the host sanitizers
 # (tests/test_pack_model.py compares them with the literal loop of tests/pack_model.py)
 build/pack_plan_host: tools/pack_plan_host.cpp $(CSRC)/kcdc_pack_format.h $(CSRC)/kcdc_internal.h
+	@mkdir -p build
+	g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan -I$(CSRC) $< -o $@
+
+# The content-ID set's decisions (probe, outcome, commit, lookup, refusal) run sequentially on the CPU
+# under the host sanitizers, every table of its exact size (tests/test_dedup_model.py compares them
+# with the literal loop of tests/dedup_model.py)
+build/dedup_host: tools/dedup_host.cpp $(CSRC)/kcdc_dedup_format.h $(CSRC)/kcdc_internal.h
 	@mkdir -p build
 	g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan -I$(CSRC) $< -o $@
 

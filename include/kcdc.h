@@ -34,6 +34,7 @@ extern "C" {
 #define KCDC_EOVERFLOW (-75) /* caller-provided cut capacity too small */
 #define KCDC_EFBIG (-27)     /* chunk too long to encrypt (>= 1 GiB) */
 #define KCDC_EBADMSG (-74)   /* sealed chunk failed authentication */
+#define KCDC_ENOSPC (-28)    /* the content-ID set cannot take the call's IDs */
 
 /* counts[i] value of every stream of a batch launch that could not complete on the
  * device (a wave gave up waiting in the work queue): the launch's cut lists are invalid.
@@ -613,8 +614,9 @@ int kcdc_ecc_repair_chunks_device(const char* algorithm, int32_t overhead_percen
  *   4. append to the pack: PackOffset = the pack's length, PackedLength = the stored length; a pack
  *      whose length is >= max_pack_size after the append is closed and the next content opens a new
  *      one, whose length starts at pack_lead (content_manager.go:314-334).
- * The host keeps the dedup decision, blob IDs, the preamble's bytes, the postamble, the index and
- * the split by pack prefix: one call packs the contents of one prefix.
+ * The dedup decision is d_keep, the host's or kcdc_dedup_claim_device's (below).  The host keeps
+ * blob IDs, the preamble's bytes, the postamble, the index and the split by pack prefix: one call
+ * packs the contents of one prefix.
  * kcdc_pack_params: max_pack_size 1..2^30; pack_lead: bytes left free at the head of every new pack
  *   (the host fills them); open_fill: 0, or the length (< max_pack_size) of an open pack that pack 0
  *   of this call continues; max_total_bytes (<= 2^40): the caller's bound on the sum of the packed
@@ -671,6 +673,61 @@ int kcdc_pack_chunks_device(const kcdc_pack_params* params, const uint8_t* d_dat
                             uint32_t packs_cap, uint64_t* d_totals, void* d_work, uint64_t work_bytes,
                             void* hip_stream);
 
+/* ------------------------------------------------------------- content dedup
+ * WriteContent's lookup between hashData and addToPackUnlocked (repo/content/content_manager.go:
+ * 812-842) on the device: a set of content IDs in device memory, and a claim call that turns a batch
+ * of digests into the d_keep mask kcdc_pack_chunks_device takes, with no host round trip.
+ * A key is `prefix` (the content ID's one-letter prefix, index.IDPrefix; 0 for none) and id_len hash
+ * bytes at d_ids + i * id_stride (any alignment, id_stride >= id_len).  id_len is fixed per set,
+ * 16..32 (every kcdc_hash_size).  Two keys are equal iff the prefix and all id_len bytes are equal.
+ * kcdc_dedup_new: a set for up to max_keys (1..2^31) keys on `device`; all device memory the set
+ *   ever uses, kcdc_dedup_bytes(id_len, max_keys), is allocated here.  NULL + kcdc_last_error.
+ * kcdc_dedup_claim_device: the WriteContent decision, as if the n IDs were presented one after
+ *   another in index order.  d_keep[i] = 1 iff the key was not in the set before the call and no
+ *   j < i of the call has an equal key, else 0.  d_first[i] (may be NULL): the lowest index of the
+ *   call with an equal key (i itself exactly when d_keep[i] == 1), or KCDC_DEDUP_KNOWN if the key
+ *   was in the set before the call.  After the call every distinct key of the call is in the set.
+ *   d_totals[0]: the call's status (0, or KCDC_ENOSPC as a 64-bit two's complement value);
+ *   d_totals[1]: keys newly stored; d_totals[2]: keys stored in all.  The results are a function of
+ *   the set's contents and the ID array alone, whatever the grid and the scheduling.
+ * kcdc_dedup_insert_device: claim without the per-ID outputs, for loading the committed index.  The
+ *   host leaves deleted entries out, so a deleted content is written again
+ *   (content_manager.go:825-840).
+ * kcdc_dedup_lookup_device: d_known[i] = 1 iff the key is in the set, else 0; the set is unchanged.
+ * kcdc_dedup_grow_device: inserts every key of `from` into `to` (same id_len, same device): the
+ *   way to enlarge a full set.  `from` is unchanged.
+ * kcdc_dedup_clear_device: empties the set.
+ * kcdc_dedup_count: keys stored, after waiting for hip_stream; or a negative KCDC_E* code.
+ * Refusal, decided on the device for the whole call: claim, insert and grow are refused if the keys
+ *   stored plus n (grow: plus the keys of `from`) exceed max_keys, whether or not some of the IDs
+ *   are duplicates, so the host can predict it.  A refused call changes nothing in the set and
+ *   gives d_totals = {KCDC_ENOSPC, 0, keys stored}, every d_keep[i] = 0 and every d_first[i] =
+ *   KCDC_DEDUP_KNOWN.  No partial insert is ever visible.
+ * Every *_device call is asynchronous on hip_stream: no host synchronisation, allocation or copy;
+ *   every array is device memory and must stay allocated until the work finishes.  n == 0 launches
+ *   nothing but writes d_totals.  Calls on one set (for grow: on either set) must be ordered by the
+ *   caller, on one stream or by events: the set does no locking, and two calls in flight on one set
+ *   corrupt it.  Different sets are independent.
+ *   Returns KCDC_EINVAL (null argument, id_len outside 16..32, id_stride < id_len, max_keys 0 or
+ *   above 2^31, mismatched sets), KCDC_ENOMEM or KCDC_ENODEV before anything is launched.
+ * kcdc_test_dedup_home (test hook, host arithmetic): the first slot probed for a key in a set of
+ *   this shape; UINT64_MAX for a bad shape. */
+typedef struct kcdc_dedup kcdc_dedup;
+#define KCDC_DEDUP_KNOWN UINT32_MAX /* d_first[i]: the ID was in the set before this call */
+kcdc_dedup* kcdc_dedup_new(int device, uint32_t id_len, uint64_t max_keys);
+void kcdc_dedup_free(kcdc_dedup* t);
+uint64_t kcdc_dedup_bytes(uint32_t id_len, uint64_t max_keys); /* device memory a set takes (0: bad shape); host only */
+int64_t kcdc_dedup_count(kcdc_dedup* t, void* hip_stream);
+int kcdc_dedup_clear_device(kcdc_dedup* t, void* hip_stream);
+int kcdc_dedup_claim_device(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                            uint8_t* d_keep, uint32_t* d_first, uint64_t* d_totals, void* hip_stream);
+int kcdc_dedup_insert_device(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                             uint64_t* d_totals, void* hip_stream);
+int kcdc_dedup_lookup_device(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                             uint8_t* d_known, void* hip_stream);
+int kcdc_dedup_grow_device(kcdc_dedup* from, kcdc_dedup* to, uint64_t* d_totals, void* hip_stream);
+uint64_t kcdc_test_dedup_home(uint32_t id_len, uint64_t max_keys, uint8_t prefix, const uint8_t* id);
+
 /* ------------------------------------------------------------- testing
  * Hooks for the library's own tests (not part of the splitter surface).
  * kcdc_test_set: process-wide knobs read by every later batch launch.
@@ -710,7 +767,8 @@ int kcdc_pack_chunks_device(const kcdc_pack_params* params, const uint8_t* d_dat
  *                         decode of kcdc_decompress_chunks_device and the content decode of
  *                         kcdc_inflate_chunks_device (their CRC passes follow), and the entropy and
  *                         execute passes of kcdc_zstd_decode_chunks_device (zstd_entropy_kernel,
- *                         zstd_execute_kernel; its checksum pass follows); 0: the default (no
+ *                         zstd_execute_kernel; its checksum pass follows), and the probe, outcome,
+                         commit and lookup kernels of kcdc_dedup_*; 0: the default (no
  *                         cap); negative: KCDC_EINVAL.  Same results from any grid: with one
  *                         workgroup a few hundred tiny chunks make every wave walk many chunks and
  *                         take many tickets, which otherwise needs tens of thousands.

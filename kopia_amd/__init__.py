@@ -15,6 +15,8 @@ kernels in ``libkcdc.so``; see DESIGN.md.  Public Python surface:
   chunks with the content manager's keep-or-drop rule (``repo/compression``; ``Compressor``).
 * :mod:`kopia_amd.packing` — compress, seal, ECC and placement in packs in one device call
   (``repo/content``: ``maybeCompressAndEncryptDataForPacking``, ``addToPackUnlocked``; ``Packer``).
+* :mod:`kopia_amd.dedup` — the set of known content IDs on the device and the claim call that
+  turns a batch of digests into the pack call's keep mask (``WriteContent``'s lookup; ``ContentSet``).
 """
 from . import _lib  # noqa: F401
 from . import compression, encryption, hashing  # noqa: F401

@@ -28,7 +28,9 @@ KCDC_EINVAL = -22
 KCDC_EOVERFLOW = -75
 KCDC_EFBIG = -27
 KCDC_EBADMSG = -74
+KCDC_ENOSPC = -28
 KCDC_PACK_SKIPPED = 1  # status of a chunk that d_keep left out of a pack call
+KCDC_DEDUP_KNOWN = 0xFFFFFFFF  # d_first[i] of a claim: the ID was in the set before the call
 KCDC_ECC_DAMAGED = 1  # status of a decoded chunk with failed shards, before the repair
 
 KIND_FIXED, KIND_BUZHASH, KIND_RABINKARP = 0, 1, 2
@@ -171,6 +173,16 @@ _SIGS = {
     "kcdc_pack_chunks_device": (C.c_int, [C.POINTER(PackParams), _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32,
                                           C.c_uint32, _P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint64,
                                           _P]),
+    "kcdc_dedup_new": (_P, [C.c_int, C.c_uint32, C.c_uint64]),
+    "kcdc_dedup_free": (None, [_P]),
+    "kcdc_dedup_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64]),
+    "kcdc_dedup_count": (C.c_int64, [_P, _P]),
+    "kcdc_dedup_clear_device": (C.c_int, [_P, _P]),
+    "kcdc_dedup_claim_device": (C.c_int, [_P, C.c_uint8, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    "kcdc_dedup_insert_device": (C.c_int, [_P, C.c_uint8, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "kcdc_dedup_lookup_device": (C.c_int, [_P, C.c_uint8, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "kcdc_dedup_grow_device": (C.c_int, [_P, _P, _P, _P]),
+    "kcdc_test_dedup_home": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint8, _P]),
 }
 
 

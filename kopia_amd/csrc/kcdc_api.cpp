@@ -16,6 +16,7 @@
 #include "../../include/kcdc.h"
 #include "kcdc_hip.h"
 #include "kcdc_internal.h"
+#include "kcdc_dedup_format.h"
 #include "kcdc_pack_format.h"
 
 namespace kcdc {
@@ -1191,4 +1192,125 @@ extern "C" int kcdc_pack_chunks_device(const kcdc_pack_params* params, const uin
     }
     return launch_pack(r, d_data, d_offsets, d_lens, d_keep, nchunks, d_ids, id_len, id_stride, d_nonces, d_pack,
                        pack_cap, d_entries, d_packs, packs_cap, d_totals, d_work, work_bytes, hip_stream);
+}
+
+// ======================================================= content dedup
+// Parameter checks of the content-ID set; the kernels are in kcdc_dedup.hip and every decision in
+// kcdc_dedup_format.h.
+struct kcdc_dedup {
+    DedupSet s;
+};
+
+extern "C" uint64_t kcdc_dedup_bytes(uint32_t id_len, uint64_t max_keys) {
+    if (!dedupfmt::valid_shape(id_len, max_keys)) {
+        set_error(KCDC_EINVAL, "id_len must be 16..32 and max_keys 1..2^31");
+        return 0;
+    }
+    return dedupfmt::layout(id_len, max_keys).total;
+}
+
+extern "C" uint64_t kcdc_test_dedup_home(uint32_t id_len, uint64_t max_keys, uint8_t prefix, const uint8_t* id) {
+    if (!dedupfmt::valid_shape(id_len, max_keys) || !id) {
+        set_error(KCDC_EINVAL, "id_len must be 16..32, max_keys 1..2^31 and id non-null");
+        return UINT64_MAX;
+    }
+    return dedupfmt::home_slot(dedupfmt::key_hash(prefix, id), dedupfmt::slot_count(max_keys));
+}
+
+extern "C" kcdc_dedup* kcdc_dedup_new(int device, uint32_t id_len, uint64_t max_keys) {
+    if (!dedupfmt::valid_shape(id_len, max_keys)) {
+        set_error(KCDC_EINVAL, "id_len must be 16..32 and max_keys 1..2^31");
+        return nullptr;
+    }
+    if (check_device(device) != KCDC_OK) return nullptr;
+    DeviceGuard g(device);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
+        set_error(KCDC_EIO, "device attribute query failed");
+        return nullptr;
+    }
+    const dedupfmt::Layout l = dedupfmt::layout(id_len, max_keys);
+    void* base = nullptr;
+    if (hipMalloc(&base, l.total) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(KCDC_ENOMEM, "hipMalloc of the content-ID set failed (kcdc_dedup_bytes)");
+        return nullptr;
+    }
+    kcdc_dedup* t = new kcdc_dedup{DedupSet{device, id_len, max_keys, static_cast<uint8_t*>(base),
+                                            static_cast<uint32_t>(cus) * 4u}};
+    if (dedup_launch_clear(t->s, nullptr) != 0 || hipStreamSynchronize(nullptr) != hipSuccess) {
+        set_error(KCDC_EIO, "clearing the new content-ID set failed");
+        kcdc_dedup_free(t);
+        return nullptr;
+    }
+    return t;
+}
+
+extern "C" void kcdc_dedup_free(kcdc_dedup* t) {
+    if (!t) return;
+    DeviceGuard g(t->s.device);
+    (void)hipFree(t->s.base);
+    delete t;
+}
+
+extern "C" int64_t kcdc_dedup_count(kcdc_dedup* t, void* hip_stream) {
+    if (!t) return set_error(KCDC_EINVAL, "null argument");
+    DeviceGuard g(t->s.device);
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)), "hipStreamSynchronize");
+    uint64_t c = 0;
+    const dedupfmt::Layout l = dedupfmt::layout(t->s.id_len, t->s.max_keys);
+    HIP_TRY(hipMemcpy(&c, t->s.base + l.scal + 8u * dedupfmt::kStored, 8, hipMemcpyDeviceToHost), "hipMemcpy(count)");
+    return static_cast<int64_t>(c);
+}
+
+extern "C" int kcdc_dedup_clear_device(kcdc_dedup* t, void* hip_stream) {
+    if (!t) return set_error(KCDC_EINVAL, "null argument");
+    DeviceGuard g(t->s.device);
+    return dedup_launch_clear(t->s, hip_stream);
+}
+
+// claim (d_keep set) and insert (d_keep and d_first null)
+static int dedup_claim(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                       uint8_t* d_keep, uint32_t* d_first, uint64_t* d_totals, void* hip_stream) {
+    if (!t || !d_totals || (n != 0 && !d_ids)) return set_error(KCDC_EINVAL, "null argument");
+    if (id_stride < t->s.id_len) return set_error(KCDC_EINVAL, "id_stride must be >= id_len");
+    DeviceGuard g(t->s.device);
+    if (n == 0) {  // no launch: status 0, nothing new, the count as it stands on the stream
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        const dedupfmt::Layout l = dedupfmt::layout(t->s.id_len, t->s.max_keys);
+        HIP_TRY(hipMemsetAsync(d_totals, 0, 16, st), "hipMemsetAsync(d_totals)");
+        HIP_TRY(hipMemcpyAsync(d_totals + 2, t->s.base + l.scal + 8u * dedupfmt::kStored, 8, hipMemcpyDeviceToDevice, st),
+                "hipMemcpyAsync(d_totals)");
+        return KCDC_OK;
+    }
+    return dedup_launch_claim(t->s, nullptr, prefix, d_ids, id_stride, n, d_keep, d_first, d_totals, hip_stream);
+}
+
+extern "C" int kcdc_dedup_claim_device(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                                       uint8_t* d_keep, uint32_t* d_first, uint64_t* d_totals, void* hip_stream) {
+    if (n != 0 && !d_keep) return set_error(KCDC_EINVAL, "null argument");
+    return dedup_claim(t, prefix, d_ids, id_stride, n, d_keep, d_first, d_totals, hip_stream);
+}
+
+extern "C" int kcdc_dedup_insert_device(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                                        uint64_t* d_totals, void* hip_stream) {
+    return dedup_claim(t, prefix, d_ids, id_stride, n, nullptr, nullptr, d_totals, hip_stream);
+}
+
+extern "C" int kcdc_dedup_lookup_device(kcdc_dedup* t, uint8_t prefix, const uint8_t* d_ids, uint32_t id_stride, uint32_t n,
+                                        uint8_t* d_known, void* hip_stream) {
+    if (!t || (n != 0 && (!d_ids || !d_known))) return set_error(KCDC_EINVAL, "null argument");
+    if (id_stride < t->s.id_len) return set_error(KCDC_EINVAL, "id_stride must be >= id_len");
+    if (n == 0) return KCDC_OK;
+    DeviceGuard g(t->s.device);
+    return dedup_launch_lookup(t->s, prefix, d_ids, id_stride, n, d_known, hip_stream);
+}
+
+extern "C" int kcdc_dedup_grow_device(kcdc_dedup* from, kcdc_dedup* to, uint64_t* d_totals, void* hip_stream) {
+    if (!from || !to || !d_totals) return set_error(KCDC_EINVAL, "null argument");
+    if (from == to) return set_error(KCDC_EINVAL, "a set cannot grow into itself");
+    if (from->s.id_len != to->s.id_len) return set_error(KCDC_EINVAL, "the two sets must have the same id_len");
+    if (from->s.device != to->s.device) return set_error(KCDC_EINVAL, "the two sets must be on one device");
+    DeviceGuard g(to->s.device);
+    return dedup_launch_claim(to->s, &from->s, 0, nullptr, 0, 0, nullptr, nullptr, d_totals, hip_stream);
 }

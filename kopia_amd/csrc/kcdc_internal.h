@@ -44,7 +44,8 @@ int& test_hash_lanes();
 int test_set_deflate_limit(bool cl, int64_t value);  // kcdc_test_set(KCDC_TEST_DEFLATE_MAXB / _CL_MAXB)
 uint64_t& test_id_ring_bytes();  // kcdc_test_set(KCDC_TEST_ID_RING): the writers' ID ring size (0: default)
 // kcdc_test_set(KCDC_TEST_CHUNK_GRID): the most workgroups a persistent per-chunk kernel is launched
-// with (crypt_units / gcm_units, decode_blocks, inflate, zstd_entropy, zstd_execute); 0: no cap.
+// with (crypt_units / gcm_units, decode_blocks, inflate, zstd_entropy, zstd_execute, the pack gather,
+// the dedup probe / outcome / commit / lookup); 0: no cap.
 uint32_t& test_chunk_grid();
 inline uint32_t cap_chunk_grid(uint32_t grid) {
     const uint32_t cap = test_chunk_grid();

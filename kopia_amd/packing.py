@@ -65,7 +65,9 @@ class Packer:
                            id_len: int = 16, id_stride: int | None = None):
         """Pack chunk i = [offsets[i], +lengths[i]) of the device bytes at data_ptr; d_ids: the
         content IDs (device uint8, id_stride bytes apart), d_nonces: 12 bytes per chunk; keep: an
-        optional 0/1 mask.  max_total_bytes is taken from the kept lengths.
+        optional 0/1 mask, a host array or a device uint8 tensor (ContentSet.claim's, still being
+        computed on `stream`).  max_total_bytes is taken from the kept lengths; with a device
+        mask the host cannot know them and takes every admissible length, a valid bound.
         Returns device tensors (d_pack uint8, entries int32[n, 6], packs uint8[rows, 24], totals
         int64[2]); read entries and packs with entries_numpy / packs_numpy after synchronising.
         Asynchronous on `stream`."""
@@ -74,7 +76,11 @@ class Packer:
         if stream is None:
             stream = torch.cuda.current_stream(device)
         lens = np.asarray(lengths, dtype=np.int64)
-        mask = None if keep is None else np.asarray(keep, dtype=np.uint8)
+        on_device = hasattr(keep, "data_ptr")
+        if on_device and (keep.dtype != torch.uint8 or keep.dim() != 1 or keep.shape[0] != n
+                          or not keep.is_contiguous() or not keep.is_cuda):
+            raise ValueError("keep: a contiguous device uint8 tensor of one byte per chunk")
+        mask = None if keep is None or on_device else np.asarray(keep, dtype=np.uint8)
         kept = lens if mask is None else lens[mask != 0]
         run = self.with_total(int(kept[kept <= (1 << 30) - 64].sum()))
         pack_bytes, max_packs, wb = run.bounds(n)
@@ -85,7 +91,7 @@ class Packer:
             totals = torch.empty(2, dtype=torch.int64, device=device)
             d_offs = torch.as_tensor(np.asarray(offsets, dtype=np.int64)).to(device)
             d_lens = torch.as_tensor(lens).to(device)
-            d_keep = None if mask is None else torch.as_tensor(mask).to(device)
+            d_keep = keep if on_device else None if mask is None else torch.as_tensor(mask).to(device)
             work = torch.empty(wb + 256, dtype=torch.uint8, device=device)
         wp = (work.data_ptr() + 255) & ~255
         _lib.check(run.pack_chunks_raw(data_ptr, d_offs, d_lens, d_keep, n, d_ids, id_len,
